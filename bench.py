@@ -10,9 +10,19 @@ N > 1 defaults to weak scaling: rank r owns rollouts [r*K, (r+1)*K) of a K*N-rol
 autorally runs AutoRally-NN K = 16384, T = 150 as the primary workload instead (7x the work per rollout: the configuration
 where sharding a fixed problem can pay — DESIGN.md §6).
 
-The timed region is EXACTLY --steps iterations between barrier + synchronize; because 20 Cartpole steps are 0.7 ms, the region
-is repeated (each repetition bracketed the same way) until at least --min-time seconds have been timed in total and
-ms_per_step is the median repetition — the driver's --steps 20 and a 2000-step run then agree.
+The timed region is EXACTLY --steps iterations between barrier + synchronize, after --warmup untimed ones, and ms_per_step is
+its time divided by --steps.  --min-time S repeats the region (each repetition bracketed the same way) until at least S
+seconds have been timed in total; ms_per_step is then the median repetition.
+
+A plain run does only what the headline needs: set up, warm up, time the region, print the JSON line.
+--dump-outputs DIR writes what the last timed iteration computed, as a caller of mppi_optimize reads it back, into
+DIR/<name>.npy: optimal_control [D][T][C] (u*), trajectory_costs [D][K] and statistics [D][5] (baseline, normalizer,
+free-energy mean, variance, modified variance), float32.  The inputs (x0, the seed, the Philox generations) depend on the
+arguments only, so two builds run with the same arguments can be compared output for output; --min-time, whose repetitions
+depend on measured time, is refused together with it.
+--full adds everything else the line reports: the roofline, issue floor and latency model of the headline kernel, the
+secondary workloads, compute_control latency and the CPU baseline (N = 1), the exchange paths and the other scaling mode and
+workload (N > 1).  --primary-only and --no-cpu-baseline trim a --full run.
 
 roofline: algorithmic bytes of the dominant kernel (rolloutKernel) per launch, B_alg = 4*(2*K*T*C + 2*K + 2*T*C)
 (SURVEY.md §8d), divided by its average duration measured with HIP events on the engine's own stream.
@@ -661,10 +671,30 @@ def np_tile(x, d):
     return np.tile(x, (d, 1))
 
 
+def timed_outputs(eng):
+    """what a caller of mppi_optimize reads back after the last iteration: u* [D][T][C], the trajectory costs [D][K_local]
+    and the statistics [D][5] (baseline, normalizer, free-energy mean, variance, modified variance)"""
+    import numpy as np
+    st = eng.getStats()
+    systems = (st.real_sys, st.nominal_sys)[:eng.num_systems]
+    stats = np.array([[s.baseline, s.normalizer, s.free_energy_mean, s.free_energy_variance, s.free_energy_modified_variance]
+                      for s in systems], np.float32)
+    return {"optimal_control": eng.getOptimalControlSeq(), "trajectory_costs": eng.getSampledCostSeq(), "statistics": stats}
+
+
+def dump_outputs(outputs, directory):
+    """DIR/<name>.npy, float32"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def self_launch(n_gpus):
-    """`python3 bench.py --gpus N` with no launcher around it: re-exec under torch.distributed.run, one rank per GPU
-    (the driver's own form for N > 1; both forms end in the same main())"""
+    """`python3 bench.py --gpus N` with no launcher around it: run torch.distributed.run as a child process, one rank per
+    GPU, and leave with its exit status (the driver's own form for N > 1; both forms end in the same main())"""
     import socket
+    import subprocess
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
@@ -674,7 +704,8 @@ def self_launch(n_gpus):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n_gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    rc = subprocess.call(cmd, env=env)
+    sys.exit(128 - rc if rc < 0 else rc)  # a launcher killed by signal n leaves with 128 + n, as a shell reports it
 
 
 class ShardedRun:
@@ -807,24 +838,28 @@ class ShardedRun:
                 raise RuntimeError("ranks disagree on u* after the first exchanged iteration")
         return check
 
-    # ---- the timed region
+    # ---- the timed region (torch only where there are ranks to coordinate: one GPU needs nothing but the library)
+    def _torch_synchronize(self):
+        if self.dist is not None:
+            import torch
+            torch.cuda.synchronize()
+
     def barrier(self):
-        import torch
         if self.dist is not None:
             self.dist.barrier()
-        torch.cuda.synchronize()
+        self._torch_synchronize()
         self.eng.synchronize()
 
     def timed_region(self, steps):
         """EXACTLY `steps` iterations between barrier + synchronize on both sides; max over ranks"""
-        import torch
         self.barrier()
         t0 = time.perf_counter()
         self.run(steps)
-        torch.cuda.synchronize()
+        self._torch_synchronize()
         self.barrier()
         dt_ = time.perf_counter() - t0
         if self.dist is not None:
+            import torch
             tt = torch.tensor([dt_], dtype=torch.float64)
             self.dist.all_reduce(tt, op=self.dist.ReduceOp.MAX)
             dt_ = float(tt.item())
@@ -913,17 +948,27 @@ def main():
                          "in total) split over the GPUs — north_star's 'Cartpole (K=16384, T=100) at 1/2/4/8'; the other one "
                          "is reported beside it in the same JSON line")
     ap.add_argument("--workload", choices=["cartpole", "autorally"], default="cartpole")
-    ap.add_argument("--min-time", type=float, default=0.25, help="repeat the K-step timed region until this many seconds are timed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--primary-only", action="store_true", help="skip the secondary legs (AutoRally-NN, LSTM+colored, DI-Tube, RACER elevation)")
+    ap.add_argument("--min-time", type=float, default=None,
+                    help="repeat the K-step timed region until this many seconds are timed (default: time it once; the "
+                         "--full legs beside the headline: 0.25)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, secondary legs, compute_control, CPU baseline "
+                         "(N = 1); exchange paths, the other scaling mode and workload (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write u*, trajectory costs and statistics of the last timed iteration to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--primary-only", action="store_true",
+                    help="--full: skip the secondary legs (AutoRally-NN, LSTM+colored, DI-Tube, RACER elevation)")
     args = ap.parse_args()
+    if args.dump_outputs and args.min_time is not None:
+        ap.error("--dump-outputs needs the timed region run once: with --min-time the number of iterations before the dump "
+                 "depends on measured time")
 
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and "RANK" not in os.environ:
-        self_launch(args.gpus)  # does not return
+        self_launch(args.gpus)  # does not return: exits with the ranks' status
 
     import numpy as np
-    import torch
-    import mppi_generic_amd as m  # noqa: F401
+    import mppi_generic_amd as m
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -932,10 +977,11 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     n_gpus = args.gpus
     assert world == n_gpus, "--gpus %d but WORLD_SIZE=%d" % (n_gpus, world)
-    assert torch.cuda.is_available(), "bench.py needs a GPU; the product has no CPU path"
-    torch.cuda.set_device(local_rank)
+    assert m.load_library().mppi_device_count() > local_rank, "bench.py needs a GPU; the product has no CPU path"
     dist = None
     if world > 1:
+        import torch
+        torch.cuda.set_device(local_rank)
         # control plane only (barrier, max over ranks, shipping mailbox handles / the RCCL id): gloo.  The DATA path is the
         # library's own P2P mailbox or RCCL communicator on the engine's stream.  (This image's torch wheel bundles a second
         # ROCm runtime; device buffers and streams of libmppi_amd.so belong to the system runtime, so torch's NCCL backend is
@@ -1002,65 +1048,69 @@ def main():
         return out
 
     # ------------------------------------------------------------------ the headline leg
-    sr, cfg, head, elapsed, reps = leg(args.workload, strong, None, args.steps, args.warmup, args.min_time)
+    sr, cfg, head, elapsed, reps = leg(args.workload, strong, None, args.steps, args.warmup, args.min_time or 0.0)
+    if args.dump_outputs and rank == 0:  # read back before any further iteration runs on the engine
+        dump_outputs(timed_outputs(sr.eng), args.dump_outputs)
     hint = sr.exchange["mode"] if world > 1 else None
     k_total, k_local, t_steps = head["global_rollouts"], head["rollouts_per_gpu"], head["num_timesteps"]
     x0 = cfg["x0"]
-    n_ev = min(200, max(20, args.steps))
-    iter_us, roll_us = sr.kernel_times_us(n_ev, elapsed / args.steps * 1e6)
-    C_dim = sr.eng.CONTROL_DIM
-    if args.workload == "autorally":
-        f_alg = 2.0 * (6 * 32 + 32 * 32 + 32 * 4) * k_local * t_steps
-        achieved = f_alg / (roll_us * 1e-6) / 1e12
-        roofline = {
-            "bound": "mfma", "kernel": "rolloutPipelineRepKernel<NeuralNetModelMFMA<7,2,3>,ARStandardCost,Gaussian,true>",
-            "achieved": round(achieved, 4), "peak": 157.3, "unit": "TFLOP/s", "frac": round(achieved / 157.3, 5),
-            "traffic": pmc_traffic("rolloutPipelineRepKernel<NeuralNetModelMFMA") if k_local == K_PER_GPU else None,
-            "traffic_static_from_profiles": PMC_FILE,
-            "algorithmic_flops_per_launch": f_alg, "avg_kernel_us": round(roll_us, 3),
-            "avg_iteration_us_event_timed": round(iter_us, 3),
-        }
-    else:
-        b_alg = 4.0 * (2.0 * k_local * t_steps * C_dim + 2.0 * k_local + 2.0 * t_steps * C_dim)
-        achieved = b_alg / (roll_us * 1e-6) / 1e9
-        # one GPU: the instantiation that merges the previous iteration's records in its sampler waves (STREAM_MERGE = true);
-        # K-sharded: the plain one, the merge is combineShardedKernel
-        tail = "false, false, true>" if world == 1 else "false, false, false>"
-        roofline = {
-            "bound": "hbm", "kernel": "rolloutPipelineKernel<CartpoleDynamics, CartpoleQuadraticCost, GaussianDistribution<"
-                                      "CartpoleDynamicsParams>, 1, true, " + tail,
-            "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 5),
-            "traffic": pmc_traffic("rolloutPipelineKernel<CartpoleDynamics", tail) if k_local == K_PER_GPU else None,
-            "traffic_static_from_profiles": PMC_FILE,
-            "pipe_utilisation_static_from_profiles": pmc_pipe_util("rolloutPipelineKernel<CartpoleDynamics", tail),
-            "traffic_source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, " + PMC_FILE + " "
-                              "(2*FETCH_SIZE + WRITE_SIZE), collected by the builder, NOT in this run: the sample tensor never "
-                              "reaches HBM, so traffic << algorithmic bytes",
-            "algorithmic_bytes_per_launch": b_alg, "avg_kernel_us": round(roll_us, 3),
-            "avg_iteration_us_event_timed": round(iter_us, 3),
-            # SURVEY.md §8d prices the roofline on the whole iteration (t_iter), the contract on the dominant kernel: both
-            "frac_on_iteration": round(b_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5),
-            "note": "the HBM roofline is the ceiling SURVEY.md §8d assigns, not the one that binds: the kernel is issue-bound on "
-                    "the dynamics wave (T dependent Euler steps per rollout, one wave per CU at K=16384 — K=32768 costs only "
-                    "~17 % more time, DESIGN.md §5); see issue_floor for a floor that does not depend on the kernel's own timing",
-        }
-        if world == 1:
-            roofline["note"] += ("; on one GPU this kernel also does the softmin merge of the previous iteration's block records "
-                                 "(in its sampler waves — until round 4 a second launch of 3.3 us + a 1.55 us boundary), so its "
-                                 "duration is the whole iteration: compare frac with (rollout + merge) of earlier rounds, "
-                                 "13.24 MB / 27.0 us = 0.061, not with the rollout kernel alone")
-        if world == 1:
-            n_launch = launches_per_iteration(sr.eng)
-            roofline["launches_per_iteration"] = n_launch
-            try:
-                roofline["issue_floor"] = issue_floor(local_rank, iter_us, roll_us, n_launch=n_launch)
-            except Exception as e:  # noqa: BLE001
-                roofline["issue_floor"] = {"error": str(e)}
-            try:
-                roofline["latency_model"] = latency_model(local_rank, iter_us, n_launch)
-            except Exception as e:  # noqa: BLE001
-                roofline["latency_model"] = {"error": str(e)}
+    roofline = None
+    if args.full:
+        n_ev = min(200, max(20, args.steps))
+        iter_us, roll_us = sr.kernel_times_us(n_ev, elapsed / args.steps * 1e6)
+        C_dim = sr.eng.CONTROL_DIM
+        if args.workload == "autorally":
+            f_alg = 2.0 * (6 * 32 + 32 * 32 + 32 * 4) * k_local * t_steps
+            achieved = f_alg / (roll_us * 1e-6) / 1e12
+            roofline = {
+                "bound": "mfma", "kernel": "rolloutPipelineRepKernel<NeuralNetModelMFMA<7,2,3>,ARStandardCost,Gaussian,true>",
+                "achieved": round(achieved, 4), "peak": 157.3, "unit": "TFLOP/s", "frac": round(achieved / 157.3, 5),
+                "traffic": pmc_traffic("rolloutPipelineRepKernel<NeuralNetModelMFMA") if k_local == K_PER_GPU else None,
+                "traffic_static_from_profiles": PMC_FILE,
+                "algorithmic_flops_per_launch": f_alg, "avg_kernel_us": round(roll_us, 3),
+                "avg_iteration_us_event_timed": round(iter_us, 3),
+            }
+        else:
+            b_alg = 4.0 * (2.0 * k_local * t_steps * C_dim + 2.0 * k_local + 2.0 * t_steps * C_dim)
+            achieved = b_alg / (roll_us * 1e-6) / 1e9
+            # one GPU: the instantiation that merges the previous iteration's records in its sampler waves (STREAM_MERGE = true);
+            # K-sharded: the plain one, the merge is combineShardedKernel
+            tail = "false, false, true>" if world == 1 else "false, false, false>"
+            roofline = {
+                "bound": "hbm", "kernel": "rolloutPipelineKernel<CartpoleDynamics, CartpoleQuadraticCost, GaussianDistribution<"
+                                          "CartpoleDynamicsParams>, 1, true, " + tail,
+                "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 5),
+                "traffic": pmc_traffic("rolloutPipelineKernel<CartpoleDynamics", tail) if k_local == K_PER_GPU else None,
+                "traffic_static_from_profiles": PMC_FILE,
+                "pipe_utilisation_static_from_profiles": pmc_pipe_util("rolloutPipelineKernel<CartpoleDynamics", tail),
+                "traffic_source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, " + PMC_FILE + " "
+                                  "(2*FETCH_SIZE + WRITE_SIZE), collected by the builder, NOT in this run: the sample tensor never "
+                                  "reaches HBM, so traffic << algorithmic bytes",
+                "algorithmic_bytes_per_launch": b_alg, "avg_kernel_us": round(roll_us, 3),
+                "avg_iteration_us_event_timed": round(iter_us, 3),
+                # SURVEY.md §8d prices the roofline on the whole iteration (t_iter), the contract on the dominant kernel: both
+                "frac_on_iteration": round(b_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5),
+                "note": "the HBM roofline is the ceiling SURVEY.md §8d assigns, not the one that binds: the kernel is issue-bound on "
+                        "the dynamics wave (T dependent Euler steps per rollout, one wave per CU at K=16384 — K=32768 costs only "
+                        "~17 % more time, DESIGN.md §5); see issue_floor for a floor that does not depend on the kernel's own timing",
+            }
+            if world == 1:
+                roofline["note"] += ("; on one GPU this kernel also does the softmin merge of the previous iteration's block records "
+                                     "(in its sampler waves — until round 4 a second launch of 3.3 us + a 1.55 us boundary), so its "
+                                     "duration is the whole iteration: compare frac with (rollout + merge) of earlier rounds, "
+                                     "13.24 MB / 27.0 us = 0.061, not with the rollout kernel alone")
+            if world == 1:
+                n_launch = launches_per_iteration(sr.eng)
+                roofline["launches_per_iteration"] = n_launch
+                try:
+                    roofline["issue_floor"] = issue_floor(local_rank, iter_us, roll_us, n_launch=n_launch)
+                except Exception as e:  # noqa: BLE001
+                    roofline["issue_floor"] = {"error": str(e)}
+                try:
+                    roofline["latency_model"] = latency_model(local_rank, iter_us, n_launch)
+                except Exception as e:  # noqa: BLE001
+                    roofline["latency_model"] = {"error": str(e)}
     exchange_info = dict(sr.exchange)
     sr.close()
     if world > 1:
@@ -1070,7 +1120,7 @@ def main():
 
     # ------------------------------------------------------------------ N > 1: the other scaling mode and the other workload
     extra = {}
-    if world > 1 and not args.primary_only:
+    if world > 1 and args.full and not args.primary_only:
         other = "autorally" if args.workload == "cartpole" else "cartpole"
         try:
             extra["exchange_paths"] = exchange_paths(args.workload, max(20, min(args.steps, 200)), max(5, min(args.warmup, 50)),
@@ -1090,7 +1140,8 @@ def main():
             if wl == "lstm_colored":
                 steps = max(5, min(args.steps, 40))
             try:
-                sr2, _, res, _, _ = leg(wl, st_, hint, steps, max(5, min(args.warmup, steps)), args.min_time)
+                sr2, _, res, _, _ = leg(wl, st_, hint, steps, max(5, min(args.warmup, steps)),
+                                        0.25 if args.min_time is None else args.min_time)
                 res["steps"] = steps
                 res["workload"] = WORKLOAD_TEXT[wl] + ", K=%d rollouts %s" % (
                     K_BASE[wl], "in total, split over the GPUs" if st_ else "per GPU")
@@ -1127,8 +1178,9 @@ def main():
             "timed_region_s": round(elapsed, 6),
             "timed_total_s": round(float(sum(reps)), 6),
             "finite": head["finite"],
-            "roofline": roofline,
         }
+        if args.full:
+            out["roofline"] = roofline
         out.update(extra)
         if world > 1:
             out["predicted_ms_per_step_model"] = PREDICTED_MS_PER_STEP["inputs"]
@@ -1136,7 +1188,7 @@ def main():
                                      "rollout kernel is T dependent steps of one wave per CU whatever K is; sharding adds one merge "
                                      "launch and the hop) and ~N x for the weak line beside it")
         # secondary workloads of the north star (not the headline `value`)
-        if not args.primary_only and world == 1 and args.workload == "cartpole":
+        if args.full and not args.primary_only and world == 1 and args.workload == "cartpole":
             for key, leg_fn in (("autorally_nn", autorally_leg), ("lstm_colored", lstm_colored_leg), ("di_tube", di_tube_leg),
                                 ("racer_elevation", racer_elevation_leg), ("robust_autorally_nn", robust_autorally_leg),
                                 ("robust_double_integrator", robust_di_leg), ("robust_racer", robust_racer_leg),
@@ -1148,14 +1200,14 @@ def main():
                         out[key] = leg_fn(local_rank)
                 except Exception as e:  # noqa: BLE001
                     out[key] = {"error": str(e)}
-        if world == 1 and args.workload == "cartpole":
+        if args.full and world == 1 and args.workload == "cartpole":
             try:
                 out["compute_control"] = compute_control_latency(local_rank, x0)
                 out["compute_control_latency_us"] = out["compute_control"]["control_ready_us"]
                 out["compute_control_calls_per_s"] = round(1e6 / out["compute_control"]["closed_loop_period_us"], 1)
             except Exception as e:  # noqa: BLE001
                 out["compute_control"] = {"error": str(e)}
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(cfg, budget_s=12.0 if args.workload == "cartpole" else 20.0)
         print(json.dumps(out), flush=True)
     if dist is not None:

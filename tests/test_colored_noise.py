@@ -65,16 +65,25 @@ def test_oracle_matches_reference_script_golden(name, flavour):
     assert np.abs(got - y).max() <= 3e-6 * max(1.0, np.abs(y).max()), np.abs(got - y).max()
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/scripts/colored_noise.py"), reason="reference tree not present")
-def test_golden_is_what_the_reference_script_produces_now():
-    """in the build container: re-import the reference script and regenerate one case -> identical to the committed fixture"""
+def test_golden_draws_regenerate_from_seed_and_outputs_match_numpy_irfft():
+    """the committed fixture, checked without the script that made it: the N(0,1) draws of every case are the generator's
+    stream for its seed (tests/golden/make_colored_noise_reference.py: two float32 draws of [K][T+1] per control, real then
+    imaginary) bit for bit, and the script's outputs agree with the independent numpy float64 irfft path above (weights and
+    sigma in float32 there, hence 5e-7 rather than equality)"""
     sys.path.insert(0, os.path.dirname(GOLDEN))
     import make_colored_noise_reference as mk
-    mod = mk.load_reference_module()
     for i, (name, K, T, exps, fmin) in enumerate(mk.CASES):
-        z, y = mk.run_case(mod, K, T, exps, fmin, seed=1000 + i)
-        zg, yg, _, _ = _golden(name)
-        assert np.array_equal(z, zg) and np.array_equal(y, yg)
+        zg, yg, eg, fg = _golden(name)
+        assert eg == list(exps) and fg == fmin
+        rng = np.random.Generator(np.random.Philox(1000 + i))
+        z = np.zeros((K, len(exps), T + 1, 2), np.float32)
+        for c in range(len(exps)):
+            z[:, c, :, 0] = rng.standard_normal((K, T + 1), dtype=np.float32)
+            z[:, c, :, 1] = rng.standard_normal((K, T + 1), dtype=np.float32)
+        assert np.array_equal(z, zg), name
+        y = _numpy_reference(zg, exps, 0.0, fmin, 0)
+        assert y.shape == yg.shape
+        assert np.abs(y - yg).max() <= 5e-7 * max(1.0, np.abs(yg).max()), (name, np.abs(y - yg).max())
 
 
 @pytest.mark.parametrize("T,exps,decay,fmin,stride", [(50, [1.0, 0.5], 0.97, 0.0, 1), (200, [1.0, 1.0], 0.97, 0.0, 1),

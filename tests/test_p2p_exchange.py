@@ -262,7 +262,7 @@ def test_p2p_two_processes_share_the_gpu_through_hipipc(gpu):
 def test_bench_self_launches_two_ranks_from_plain_python(gpu):
     """`python3 bench.py --gpus 2` with NO launcher around it (the form the driver used for N = 1) spawns its own ranks,
     negotiates the exchange, and prints ONE JSON line whose headline is the strong-scaling BASELINE problem with the weak line
-    and the other workload beside it.  Both ranks share this box's one GPU (MPPI_BENCH_DEVICE=0)."""
+    and the other workload beside it (--full).  Both ranks share one GPU (MPPI_BENCH_DEVICE=0)."""
     import json
     import subprocess
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -270,7 +270,7 @@ def test_bench_self_launches_two_ranks_from_plain_python(gpu):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                        "--min-time", "0.05"], capture_output=True, text=True, timeout=900, env=env, cwd=repo)
+                        "--min-time", "0.05", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=repo)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

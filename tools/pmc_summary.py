@@ -42,7 +42,7 @@ def main():
         if k.startswith("rollout") and fetch.get(k) and write.get(k):
             e["hbm_traffic_bytes_per_launch"] = (2.0 * fetch[k]["avg_kb"] + write[k]["avg_kb"]) * 1024.0
         kernels[k] = e
-    json.dump({"command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python bench.py --steps 100 "
+    json.dump({"command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python bench.py --full --steps 100 "
                           "--warmup 20 --no-cpu-baseline ; the same with --pmc WRITE_SIZE (separate passes)",
                "units": "rocprofv3 FETCH_SIZE / WRITE_SIZE are KiB per dispatch",
                "correction": "gfx950: FETCH_SIZE counts 128-B requests at 64 B -> doubled; WRITE_SIZE as reported",
