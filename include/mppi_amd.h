@@ -469,6 +469,9 @@ mppi_status mppi_comm_init_rccl(mppi_handle h, const void* unique_id, size_t nby
  *  [0] written the inputs, [1] enqueued the ingest, [2] the iterations, [3] the merge, [4] the finalize kernel, [5] seen the
  *  control-ready flag, [6] copied the results out; out8[7] is unused (tools/compute_control_host_timing.py) */
 mppi_status mppi_debug_host_stamps(mppi_handle h, double* out8);
+/** diagnostics: the device, pinned and mapped allocations of the engine and the in-tree models alive in this process, and their
+ *  bytes (a plugin's own allocations are not counted) */
+mppi_status mppi_debug_live_allocations(int64_t* count, int64_t* bytes);
 
 /* ---------------------------------------------------------------- kernel-level operators ------------------------- */
 /* Host-buffer wrappers around single kernels, mirroring the reference's launch wrappers; used by the kernel-level

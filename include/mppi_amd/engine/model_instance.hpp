@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "mppi_amd.h"
+#include "hip_owned.hpp"
 #include "kernarg_view.hpp"
 #include "rollout_kernel.hpp"
 #include "finalize_kernel.hpp"
@@ -435,8 +436,7 @@ struct ModelT : ModelBase
 {
   /* ---- Robust MPPI: block = (64 rollouts, 1, 2 systems), one lane per rollout and system ---- */
   DeviceDDP<DYN_T> fb;
-  float* gains_d = nullptr;
-  int gains_T = 0;
+  HipBuffer<float> gains_d;
   bool supportsRMPPI() const override
   {
     return RMPPI;
@@ -448,26 +448,22 @@ struct ModelT : ModelBase
     {
       const size_t n = (size_t)T * DYN_T::STATE_DIM * DYN_T::CONTROL_DIM;
       hipError_t e = hipSuccess;
-      if (gains_T != T)
+      if (gains_d.size() != n)
       {
-        e = hipStreamSynchronize(stream);
-        if (e == hipSuccess && gains_d)
-          e = hipFree(gains_d);
-        gains_d = nullptr;
+        e = hipStreamSynchronize(stream);  // earlier launches may still read the old gains
         if (e == hipSuccess)
-          e = hipMalloc((void**)&gains_d, n * sizeof(float));
-        gains_T = T;
+          e = gains_d.alloc(n);
       }
       if (e == hipSuccess)
         e = hipMemcpyAsync(gains_d, gains, n * sizeof(float), hipMemcpyHostToDevice, stream);
       if (e == hipSuccess)
         e = hipStreamSynchronize(stream);
+      fb.fb_gain_traj_d_ = gains_d;  // null after a failed allocation, never a freed buffer
       if (e != hipSuccess)
       {
         err = std::string("feedback gain upload: ") + hipGetErrorString(e);
         return MPPI_ERR_HIP;
       }
-      fb.fb_gain_traj_d_ = gains_d;
       fb.num_timesteps_ = T;
       fb.accumulate_all_states_ = accumulate_all_states;
       return MPPI_OK;
@@ -884,47 +880,23 @@ struct ModelT : ModelBase
   COST_T cost;
   SAMPLING_T smp;
   /* colored noise: basis table cache */
-  float* basis_d = nullptr;
+  HipBuffer<float> basis_d;
   int basis_T = -1, basis_stride = -1;
-  size_t basis_floats = 0;
   bool basis_dirty = true;
-  float* weights_d = nullptr;
-  float* weights2_d = nullptr;
-  float* costmap_d = nullptr;
-  float* elevation_d = nullptr;
-  float* normals_d = nullptr;
+  HipBuffer<float> weights_d;
+  HipBuffer<float> weights2_d;
+  HipBuffer<float> costmap_d;
+  HipBuffer<float> elevation_d;
+  HipBuffer<float> normals_d;
   bool normals_transform_set = false;
-  float* extra_net_d[4] = { nullptr, nullptr, nullptr, nullptr };  ///< mean LSTM, mean MLP, uncertainty LSTM, uncertainty MLP
+  HipBuffer<float> extra_net_d[4];  ///< mean LSTM, mean MLP, uncertainty LSTM, uncertainty MLP
 
-  ~ModelT() override
+  /** frees the old blob, then uploads the new one */
+  static mppi_status upload(HipBuffer<float>& dst, const float* src, size_t count, hipStream_t stream, std::string& err)
   {
-    if (gains_d)
-      (void)hipFree(gains_d);
-    if (basis_d)
-      (void)hipFree(basis_d);
-    if (weights_d)
-      (void)hipFree(weights_d);
-    if (weights2_d)
-      (void)hipFree(weights2_d);
-    if (costmap_d)
-      (void)hipFree(costmap_d);
-    if (elevation_d)
-      (void)hipFree(elevation_d);
-    if (normals_d)
-      (void)hipFree(normals_d);
-    for (float* q : extra_net_d)
-      if (q)
-        (void)hipFree(q);
-  }
-
-  static mppi_status upload(float** dst, const float* src, size_t count, hipStream_t stream, std::string& err)
-  {
-    if (*dst)
-      (void)hipFree(*dst);
-    *dst = nullptr;
-    hipError_t e = hipMalloc((void**)dst, count * sizeof(float));
+    hipError_t e = dst.alloc(count);
     if (e == hipSuccess)
-      e = hipMemcpyAsync(*dst, src, count * sizeof(float), hipMemcpyHostToDevice, stream);
+      e = hipMemcpyAsync(dst, src, count * sizeof(float), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess)
       e = hipStreamSynchronize(stream);
     if (e != hipSuccess)
@@ -948,7 +920,7 @@ struct ModelT : ModelBase
                 std::to_string(count);
           return MPPI_ERR_INVALID_ARG;
         }
-        mppi_status st = upload(&weights_d, data, count, stream, err);
+        mppi_status st = upload(weights_d, data, count, stream, err);
         dyn.helper_.theta_d_ = weights_d;
         return st;
       }
@@ -982,7 +954,7 @@ struct ModelT : ModelBase
                 std::to_string(count);
           return MPPI_ERR_INVALID_ARG;
         }
-        mppi_status st = upload(&weights_d, data, count, stream, err);
+        mppi_status st = upload(weights_d, data, count, stream, err);
         dyn.lstm_.weights_d_ = weights_d;
         return st;
       }
@@ -994,7 +966,7 @@ struct ModelT : ModelBase
                 std::to_string(count);
           return MPPI_ERR_INVALID_ARG;
         }
-        mppi_status st = upload(&weights2_d, data, count, stream, err);
+        mppi_status st = upload(weights2_d, data, count, stream, err);
         dyn.lstm_.output_nn_.theta_d_ = weights2_d;
         return st;
       }
@@ -1009,7 +981,7 @@ struct ModelT : ModelBase
           err = "elevation_map: dims must be {height, width} with height*width == count";
           return MPPI_ERR_INVALID_ARG;
         }
-        mppi_status st = upload(&elevation_d, data, count, stream, err);
+        mppi_status st = upload(elevation_d, data, count, stream, err);
         auto& tex = dyn.tex_helper_.textures_[0];
         tex.data = elevation_d;
         tex.height = dims[0];
@@ -1070,11 +1042,7 @@ struct ModelT : ModelBase
         }
         // blobs of the previous shape no longer fit
         for (int k = 2 * (which - 1); k < 2 * which; k++)
-        {
-          if (extra_net_d[k])
-            (void)hipFree(extra_net_d[k]);
-          extra_net_d[k] = nullptr;
-        }
+          extra_net_d[k].reset();
         (which == 1 ? dyn.mean_lstm_d_ : dyn.unc_lstm_d_) = nullptr;
         (which == 1 ? dyn.mean_fnn_d_ : dyn.unc_fnn_d_) = nullptr;
         (which == 1 ? dyn.mean_lstm_ : dyn.unc_lstm_).weights_d_ = nullptr;
@@ -1120,7 +1088,7 @@ struct ModelT : ModelBase
           }
           return MPPI_OK;
         }
-        mppi_status st = upload(&extra_net_d[nets[i].slot], data, count, stream, err);
+        mppi_status st = upload(extra_net_d[nets[i].slot], data, count, stream, err);
         // only what was uploaded for the present shapes (a structure blob clears its network's pair)
         if (nets[i].slot == 0)
           dyn.mean_lstm_.weights_d_ = dyn.mean_lstm_d_ = extra_net_d[0];
@@ -1144,7 +1112,7 @@ struct ModelT : ModelBase
           err = "normals_map: dims must be {height, width, 4} with height*width*4 == count";
           return MPPI_ERR_INVALID_ARG;
         }
-        mppi_status st = upload(&normals_d, data, count, stream, err);
+        mppi_status st = upload(normals_d, data, count, stream, err);
         auto& tex = dyn.normals_tex_helper_.textures_[0];
         tex.data = normals_d;
         tex.height = dims[0];
@@ -1179,7 +1147,7 @@ struct ModelT : ModelBase
           err = "costmap: dims must be {height, width} with height*width == count";
           return MPPI_ERR_INVALID_ARG;
         }
-        mppi_status st = upload(&costmap_d, data, count, stream, err);
+        mppi_status st = upload(costmap_d, data, count, stream, err);
         cost.costmap_d_ = costmap_d;
         cost.height_ = dims[0];
         cost.width_ = dims[1];
@@ -1384,24 +1352,19 @@ struct ModelT : ModelBase
           sampling_distributions::buildColoredNoiseBasis(s.num_timesteps, DYN_T::CONTROL_DIM, smp.exponents_,
                                                          smp.offset_decay_rate_, smp.fmin_, s.optimization_stride, frag);
         hipError_t e = hipStreamSynchronize(stream);  // earlier launches may still read the old table
-        if (e == hipSuccess && basis_d && (basis_T != s.num_timesteps || basis_floats != frag.size()))
-        {
-          e = hipFree(basis_d);
-          basis_d = nullptr;
-        }
-        if (e == hipSuccess && !basis_d)
-          e = hipMalloc((void**)&basis_d, frag.size() * sizeof(float));
+        if (e == hipSuccess && (!basis_d || basis_T != s.num_timesteps || basis_d.size() != frag.size()))
+          e = basis_d.alloc(frag.size());
         if (e == hipSuccess)
           e = hipMemcpyAsync(basis_d, frag.data(), frag.size() * sizeof(float), hipMemcpyHostToDevice, stream);
         if (e == hipSuccess)
           e = hipStreamSynchronize(stream);  // frag is a local
+        smp.basis_d_ = basis_d;  // null after a failed allocation, never a freed buffer
         if (e != hipSuccess)
         {
           err = std::string("colored-noise basis upload: ") + hipGetErrorString(e);
           return MPPI_ERR_HIP;
         }
         basis_T = s.num_timesteps;
-        basis_floats = frag.size();
         basis_stride = s.optimization_stride;
         basis_dirty = false;
       }

@@ -30,10 +30,8 @@ mppi_status mppi_inject_noise(mppi_handle h, const float* eps, int n_iters)
   if (n_iters != h->n_eps_iters)
   {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->eps_d)
-      HIP_TRY(h, hipFree(h->eps_d));
-    h->eps_d = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&h->eps_d, n * sizeof(float)));
+    h->n_eps_iters = 0;  // with the buffer: a failed allocation leaves neither
+    HIP_TRY(h, h->eps_d.alloc(n));
     h->n_eps_iters = n_iters;
   }
   HIP_TRY(h, hipMemcpyAsync(h->eps_d, eps, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -96,7 +94,7 @@ static inline void publishInbox(mppi_handle h)
 static inline void launchIngest(mppi_handle h)
 {
   publishInbox(h);
-  hipLaunchKernelGGL(kernels::ingestKernel, dim3(1), dim3(256), 0, h->stream, h->io_in_dev, h->in_block_d, (int)h->in_floats);
+  hipLaunchKernelGGL(kernels::ingestKernel, dim3(1), dim3(256), 0, h->stream, h->io_in_h.dev(), h->in_block_d, (int)h->in_floats);
 }
 
 /** spins on a flag the finalize kernel raises in host memory; falls back to a stream synchronisation when the flag does not
@@ -252,10 +250,10 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
     if (direct)
     {
       publishInbox(h);  // the write-combined stores are out before the doorbell of the first launch
-      h->x0_src_d = h->io_in_dev + (h->x0_d - h->in_block_d);
-      h->mean_src_d = h->io_in_dev + (h->mean_d - h->in_block_d);
+      h->x0_src_d = h->io_in_h.dev() + (h->x0_d - h->in_block_d);
+      h->mean_src_d = h->io_in_h.dev() + (h->mean_d - h->in_block_d);
       a.x0_d = h->x0_src_d;
-      a.history_d = h->io_in_dev + (h->history_d - h->in_block_d);
+      a.history_d = h->io_in_h.dev() + (h->history_d - h->in_block_d);
     }
     else
     {
@@ -279,13 +277,13 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
     else
       MPPI_TRY(flushMerge(h));
     stamp(3);
-    a.control_out_d = h->io_out_dev + (h->ctrl_out_d - h->out_block_d);
-    a.state_out_d = h->io_out_dev + (h->state_out_d - h->out_block_d);
-    a.output_out_d = h->io_out_dev + (h->output_out_d - h->out_block_d);
+    a.control_out_d = h->io_out_h.dev() + (h->ctrl_out_d - h->out_block_d);
+    a.state_out_d = h->io_out_h.dev() + (h->state_out_d - h->out_block_d);
+    a.output_out_d = h->io_out_h.dev() + (h->output_out_d - h->out_block_d);
     a.stats_in_d = h->stats_d;
-    a.stats_out_d = h->io_out_dev + (h->stats_d - h->out_block_d);
+    a.stats_out_d = h->io_out_h.dev() + (h->stats_d - h->out_block_d);
     a.stats_floats = kernels::STATS_STRIDE;
-    a.flags_d = h->io_flags_dev;
+    a.flags_d = h->io_flags_h.dev();
     a.seq = ++h->io_seq;
     float* carry = nullptr;
     if (h->split_finalize)
@@ -297,7 +295,7 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
       carry = h->carry_d + (size_t)p * h->in_floats;
       a.phases = 1;
       a.carry_d = carry;
-      a.carry_src_d = direct ? h->io_in_dev : h->in_block_d;
+      a.carry_src_d = direct ? h->io_in_h.dev() : h->in_block_d;
       a.carry_floats = (int)h->in_floats;
       a.carry_mean_off = (int)(h->mean_d - h->in_block_d);
       a.carry_ready_d = reinterpret_cast<unsigned*>(h->carry_d + 2 * h->in_floats) + 2 * p;
@@ -314,7 +312,7 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
     // before it rewrites the inbox (round-5 advice: behind the finalize kernel the copy could read a half-rewritten inbox).  It
     // touches neither what the finalize kernel reads (inbox, mean_d) nor what it writes.
     if (direct && !h->split_finalize)
-      MPPI_TRY(ingest_ranges(h->io_in_dev));
+      MPPI_TRY(ingest_ranges(h->io_in_h.dev()));
     mppi_status st;
     if (fuse_records)
     {
@@ -446,13 +444,13 @@ static mppi_status computeControlTube(mppi_handle h, const float* x0, int stride
       a.smooth_mask = smooth_mask;
       a.constrain_mask = 0;
       a.constrain_mode = 0;
-      a.control_out_d = h->io_out_dev + (h->ctrl_out_d - h->out_block_d);
-      a.state_out_d = h->io_out_dev + (h->state_out_d - h->out_block_d);
-      a.output_out_d = h->io_out_dev + (h->output_out_d - h->out_block_d);
+      a.control_out_d = h->io_out_h.dev() + (h->ctrl_out_d - h->out_block_d);
+      a.state_out_d = h->io_out_h.dev() + (h->state_out_d - h->out_block_d);
+      a.output_out_d = h->io_out_h.dev() + (h->output_out_d - h->out_block_d);
       a.stats_in_d = h->stats_d;
-      a.stats_out_d = h->io_out_dev + (h->stats_d - h->out_block_d);
+      a.stats_out_d = h->io_out_h.dev() + (h->stats_d - h->out_block_d);
       a.stats_floats = 2 * kernels::STATS_STRIDE;
-      a.flags_d = h->io_flags_dev;
+      a.flags_d = h->io_flags_h.dev();
       a.seq = ++h->io_seq;
       std::string err;
       float* carry = nullptr;
@@ -626,28 +624,16 @@ static void rmBestIndex(mppi_handle h)
 static mppi_status rmEnsureCandidateBuffers(mppi_handle h)
 {
   const int n = h->num_candidates * h->samples_per_candidate;
-  if (n <= h->cand_capacity && h->num_candidates <= h->cand_capacity_nc)
+  if ((size_t)n <= h->cand_costs_d.size() && (size_t)h->num_candidates <= h->cand_strides_d.size())
     return MPPI_OK;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (h->cand_states_d)
-    (void)hipFree(h->cand_states_d);
-  if (h->cand_costs_d)
-    (void)hipFree(h->cand_costs_d);
-  if (h->cand_strides_d)
-    (void)hipFree(h->cand_strides_d);
-  if (h->cand_io_h)
-    (void)hipHostFree(h->cand_io_h);
-  h->cand_states_d = h->cand_costs_d = nullptr;
-  h->cand_strides_d = nullptr;
-  h->cand_io_h = h->cand_io_dev = nullptr;
-  HIP_TRY(h, hipHostMalloc((void**)&h->cand_io_h, sizeof(float) * ((size_t)h->num_candidates * (h->S + 1) + n),
-                           hipHostMallocMapped | hipHostMallocCoherent));
-  HIP_TRY(h, hipHostGetDevicePointer((void**)&h->cand_io_dev, h->cand_io_h, 0));
-  HIP_TRY(h, hipMalloc((void**)&h->cand_states_d, sizeof(float) * h->num_candidates * h->S));
-  HIP_TRY(h, hipMalloc((void**)&h->cand_costs_d, sizeof(float) * n));
-  HIP_TRY(h, hipMalloc((void**)&h->cand_strides_d, sizeof(int) * h->num_candidates));
-  h->cand_capacity = n;
-  h->cand_capacity_nc = h->num_candidates;
+  h->cand_states_d.reset();
+  h->cand_costs_d.reset();
+  h->cand_strides_d.reset();
+  HIP_TRY(h, h->cand_io_h.allocHost((size_t)h->num_candidates * (h->S + 1) + n, hipHostMallocMapped | hipHostMallocCoherent));
+  HIP_TRY(h, h->cand_states_d.alloc((size_t)h->num_candidates * h->S));
+  HIP_TRY(h, h->cand_costs_d.alloc(n));
+  HIP_TRY(h, h->cand_strides_d.alloc(h->num_candidates));
   return MPPI_OK;
 }
 
@@ -674,10 +660,10 @@ static mppi_status rmNominalStateTrajectory(mppi_handle h)
     a.smooth_mask = 0;
     a.constrain_mask = 0;
     a.constrain_mode = 0;
-    a.control_out_d = h->io_out_dev + (h->ctrl_out_d - h->out_block_d);
-    a.state_out_d = h->io_out_dev + (h->state_out_d - h->out_block_d);
-    a.output_out_d = h->io_out_dev + (h->output_out_d - h->out_block_d);
-    a.flags_d = h->io_flags_dev;
+    a.control_out_d = h->io_out_h.dev() + (h->ctrl_out_d - h->out_block_d);
+    a.state_out_d = h->io_out_h.dev() + (h->state_out_d - h->out_block_d);
+    a.output_out_d = h->io_out_h.dev() + (h->output_out_d - h->out_block_d);
+    a.flags_d = h->io_flags_h.dev();
     a.seq = ++h->io_seq;
     std::string err;
     const mppi_status st = h->model->launchFinalize(1, a, h->stream, err);
@@ -731,12 +717,12 @@ static mppi_status rmNominalStateAndStride(mppi_handle h, const float* state, in
   {
     // candidate states and strides stay in host memory mapped into the device (the kernel reads them once, in place), the
     // nominal control goes up with the input block: no copy command
-    std::copy(h->rm_cand_states.begin(), h->rm_cand_states.end(), h->cand_io_h);
+    std::copy(h->rm_cand_states.begin(), h->rm_cand_states.end(), h->cand_io_h.get());
     std::memcpy(h->cand_io_h + (size_t)nc * S, h->rm_cand_strides.data(), sizeof(int) * nc);
     std::copy(h->nominal_control_h.begin(), h->nominal_control_h.end(), h->io_in_h + (h->mean_d - h->in_block_d));
     launchIngest(h);
     HIP_TRY(h, hipGetLastError());
-    cand_costs_dev = h->cand_io_dev + (size_t)nc * (S + 1);
+    cand_costs_dev = h->cand_io_h.dev() + (size_t)nc * (S + 1);
   }
   else
   {
@@ -770,8 +756,8 @@ static mppi_status rmNominalStateAndStride(mppi_handle h, const float* state, in
   a.samples_per_candidate = ns;
   a.lambda = h->cfg.lambda;
   a.alpha = h->cfg.alpha;
-  a.strides_d = (h->low_latency ? reinterpret_cast<const int*>(h->cand_io_dev + (size_t)nc * S) : h->cand_strides_d) + c_lo;
-  a.states_d = (h->low_latency ? h->cand_io_dev : h->cand_states_d) + (size_t)c_lo * S;
+  a.strides_d = (h->low_latency ? reinterpret_cast<const int*>(h->cand_io_h.dev() + (size_t)nc * S) : h->cand_strides_d) + c_lo;
+  a.states_d = (h->low_latency ? h->cand_io_h.dev() : h->cand_states_d) + (size_t)c_lo * S;
   // sharded: the slice goes to the device buffer (posted from there), the assembled array to where the host reads it
   float* slice_dev = (shard_eval ? h->cand_costs_d : cand_costs_dev) + (size_t)c_lo * ns;
   a.trajectory_costs_d = slice_dev;
@@ -831,7 +817,7 @@ static mppi_status rmNominalStateAndStride(mppi_handle h, const float* state, in
   if (h->low_latency)
   {
     const unsigned seq = ++h->cand_seq;
-    hipLaunchKernelGGL(kernels::raiseFlagKernel, dim3(1), dim3(64), 0, h->stream, h->io_flags_dev + 9, seq);
+    hipLaunchKernelGGL(kernels::raiseFlagKernel, dim3(1), dim3(64), 0, h->stream, h->io_flags_h.dev() + 9, seq);
     HIP_TRY(h, hipGetLastError());
     MPPI_TRY(waitHostFlag(h, 9, seq));
     const float* costs = h->cand_io_h + (size_t)nc * (S + 1);
@@ -906,13 +892,13 @@ static mppi_status computeControlRobust(mppi_handle h, const float* x0_real, int
     a.smooth_mask = 3;
     a.constrain_mask = 0;
     a.constrain_mode = 0;
-    a.control_out_d = h->io_out_dev + (h->ctrl_out_d - h->out_block_d);
-    a.state_out_d = h->io_out_dev + (h->state_out_d - h->out_block_d);
-    a.output_out_d = h->io_out_dev + (h->output_out_d - h->out_block_d);
+    a.control_out_d = h->io_out_h.dev() + (h->ctrl_out_d - h->out_block_d);
+    a.state_out_d = h->io_out_h.dev() + (h->state_out_d - h->out_block_d);
+    a.output_out_d = h->io_out_h.dev() + (h->output_out_d - h->out_block_d);
     a.stats_in_d = h->stats_d;
-    a.stats_out_d = h->io_out_dev + (h->stats_d - h->out_block_d);
+    a.stats_out_d = h->io_out_h.dev() + (h->stats_d - h->out_block_d);
     a.stats_floats = 2 * kernels::STATS_STRIDE;
-    a.flags_d = h->io_flags_dev;
+    a.flags_d = h->io_flags_h.dev();
     a.seq = ++h->io_seq;
     std::string err;
     const mppi_status st = h->model->launchFinalize(2, a, h->stream, err);
@@ -1072,16 +1058,16 @@ static void slideSequence(std::vector<float>& u, int T, int C, int steps, const 
  *  command; the host spins on a flag raised behind the kernel (MPPI_AMD_NO_SPIN=1: a stream synchronisation instead) */
 mppi_status modelStepInPlace(mppi_handle h, float* x, float* u, float dt, int enforce)
 {
-  std::copy(x, x + h->S, h->step_pin_h);
+  std::copy(x, x + h->S, h->step_pin_h.get());
   std::copy(u, u + h->C, h->step_pin_h + h->S);
   std::string err;
-  mppi_status st = h->model->launchModelStep(h->step_pin_dev, h->step_pin_dev + h->S, dt, enforce, h->stream, err);
+  mppi_status st = h->model->launchModelStep(h->step_pin_h.dev(), h->step_pin_h.dev() + h->S, dt, enforce, h->stream, err);
   if (st != MPPI_OK)
     return fail(h, st, err);
   if (h->low_latency)
   {
     const unsigned seq = ++h->step_seq;
-    hipLaunchKernelGGL(kernels::raiseFlagKernel, dim3(1), dim3(64), 0, h->stream, h->io_flags_dev + 8, seq);
+    hipLaunchKernelGGL(kernels::raiseFlagKernel, dim3(1), dim3(64), 0, h->stream, h->io_flags_h.dev() + 8, seq);
     HIP_TRY(h, hipGetLastError());
     MPPI_TRY(waitHostFlag(h, 8, seq));
   }
@@ -1089,7 +1075,7 @@ mppi_status modelStepInPlace(mppi_handle h, float* x, float* u, float dt, int en
   {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
   }
-  std::copy(h->step_pin_h, h->step_pin_h + h->S, x);
+  std::copy(h->step_pin_h.get(), h->step_pin_h + h->S, x);
   std::copy(h->step_pin_h + h->S, h->step_pin_h + h->S + h->C, u);
   return MPPI_OK;
 }
@@ -1275,8 +1261,8 @@ mppi_status mppi_sample_noise(mppi_handle h, int optimization_stride, float* eps
   s.optimization_stride = optimization_stride;
   s.independent_noise = h->independent_noise ? 1 : 0;
   const size_t n = (size_t)h->K_local * h->TC;
-  float* out_d = nullptr;
-  HIP_TRY(h, hipMalloc((void**)&out_d, n * sizeof(float)));
+  HipBuffer<float> out_d;
+  HIP_TRY(h, out_d.alloc(n));
   std::string err;
   mppi_status st = h->model->launchNoiseDump(s, out_d, h->stream, err);
   hipError_t e = hipSuccess;
@@ -1286,7 +1272,6 @@ mppi_status mppi_sample_noise(mppi_handle h, int optimization_stride, float* eps
     if (e == hipSuccess)
       e = hipStreamSynchronize(h->stream);
   }
-  (void)hipFree(out_d);
   if (st != MPPI_OK)
     return fail(h, st, err);
   if (e != hipSuccess)

@@ -101,19 +101,19 @@ static mppi_status ensureMailbox(mppi_handle h)
   // records | flags [2][world], ticket counter (+ 3 words of padding) | aux arrays [2][MAILBOX_AUX_FLOATS] | aux flags [2][world]
   h->mbox_aux_off = 2 * world * dps + (size_t)(2 * world + 4);  // in 4-byte words from the base
   h->mbox_aux_off = (h->mbox_aux_off + 3) & ~(size_t)3;
-  h->mbox_bytes = sizeof(float) * (h->mbox_aux_off + 2 * (size_t)kernels::MAILBOX_AUX_FLOATS + 2 * (size_t)world);
-  h->mbox_bytes = (h->mbox_bytes + 4095) & ~(size_t)4095;
+  size_t floats = h->mbox_aux_off + 2 * (size_t)kernels::MAILBOX_AUX_FLOATS + 2 * (size_t)world;
+  floats = (floats + 1023) & ~(size_t)1023;  // whole 4 KiB pages
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   // uncached device memory where the runtime offers it (the mailbox is written by other agents); every access to it is a
   // system-scope atomic anyway, so ordinary device memory is a correct fallback
-  hipError_t e = hipExtMallocWithFlags((void**)&h->mbox_d, h->mbox_bytes, hipDeviceMallocUncached);
+  hipError_t e = h->mbox_d.allocExt(floats, hipDeviceMallocUncached);
   h->mbox_uncached = (e == hipSuccess);
   if (e != hipSuccess)
   {
     (void)hipGetLastError();
-    HIP_TRY(h, hipMalloc((void**)&h->mbox_d, h->mbox_bytes));
+    HIP_TRY(h, h->mbox_d.alloc(floats));
   }
-  HIP_TRY(h, hipMemsetAsync(h->mbox_d, 0, h->mbox_bytes, h->stream));
+  HIP_TRY(h, hipMemsetAsync(h->mbox_d, 0, h->mbox_d.bytes(), h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return MPPI_OK;
 }
@@ -131,7 +131,7 @@ static mppi_status resetMailboxSession(mppi_handle h)
     return MPPI_OK;  // fresh (zeroed at allocation) or never used since the last reset
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, hipMemsetAsync(h->mbox_d, 0, h->mbox_bytes, h->stream));
+  HIP_TRY(h, hipMemsetAsync(h->mbox_d, 0, h->mbox_d.bytes(), h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->xseq = 0;
   h->aseq = 0;
@@ -153,11 +153,9 @@ mppi_status mppi_p2p_mailbox_handle(mppi_handle h, void* out_bytes, size_t capac
   if (e != hipSuccess && h->mbox_uncached)
   {  // this runtime does not export uncached allocations: fall back to ordinary device memory
     (void)hipGetLastError();
-    (void)hipFree(h->mbox_d);
-    h->mbox_d = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&h->mbox_d, h->mbox_bytes));
+    HIP_TRY(h, h->mbox_d.alloc(h->mbox_d.size()));
     h->mbox_uncached = false;
-    HIP_TRY(h, hipMemsetAsync(h->mbox_d, 0, h->mbox_bytes, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->mbox_d, 0, h->mbox_d.bytes(), h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     e = hipIpcGetMemHandle(&ipc, h->mbox_d);
   }

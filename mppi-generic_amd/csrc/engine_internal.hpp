@@ -36,6 +36,7 @@
 
 #include "mppi_amd.h"
 #include "npz_reader.hpp"
+#include "mppi_amd/engine/hip_owned.hpp"
 #include "mppi_amd/engine/model_instance.hpp"
 #include "reduce_kernels.hpp"
 #include "exact_reduce_kernels.hpp"
@@ -85,6 +86,13 @@ struct mppi_handle_s
    * for a computeControl in flight); it reads the control ranges under params_mu only. */
   std::recursive_mutex mu;
   std::mutex params_mu;
+  /* Streams and events are declared first so that they are destroyed last: ~mppi_handle_s (engine_core.hip) synchronises
+   * and releases what the device may still use, then the members go in reverse order of declaration — buffers and the
+   * model's blobs before the streams and events. */
+  HipStream stream;       // the handle's stream: created, or the caller's cfg.stream (never destroyed)
+  HipStream side_stream;  // split hand-over: the trajectory phase's stream (see split_finalize)
+  HipEvent ev_side;       // recorded behind every trajectory phase: what joinSideStream orders stream behind
+  HipEvent ev_a, ev_b;    // timing: mppi_time_iterations, mppi_choose_kernel
   mppi_config cfg{};
   std::string model_name;
   std::unique_ptr<ModelBase> model;
@@ -94,68 +102,63 @@ struct mppi_handle_s
   bool pipeline = false;
   int num_blocks = 0;
   int TC = 0, PS = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   std::string last_error;
 
   /* device buffers */
   float* x0_d = nullptr;           // [D][S]
   float* mean_d = nullptr;         // [D][T][C]
-  float* costs_d = nullptr;        // [D][K_local]
-  float* partials_d = nullptr;     // [D][num_blocks][PS]: the records the NEXT rollout launch writes (+ their transposed copy)
+  HipBuffer<float> costs_d;        // [D][K_local]
+  HipBuffer<float> partials_d;     // [D][num_blocks][PS]: the records the NEXT rollout launch writes (+ their transposed copy)
   /* Streamed merge (rolloutPipelineKernel, STREAM_MERGE): the records of the last rollout launch stay un-merged in
    * pending_records_d until the next rollout launch merges them in its sampler waves — or flushMerge() runs combineKernel on
    * them, which everything that reads mean_d / stats_d does first.  Two record buffers alternate. */
-  float* partials_alt_d = nullptr;
+  HipBuffer<float> partials_alt_d;
   const float* pending_records_d = nullptr;
   unsigned long long n_rollout_launches = 0, n_merge_launches = 0;  // mppi_get_launch_counts
   bool stream_merge_enabled = true;  // MPPI_AMD_NO_STREAM_MERGE=1 switches it off (A/B)
   bool merge_control_enabled = true;  // MPPI_AMD_NO_MERGE_CONTROL=1: combineKernel + control phase as two launches (A/B, tests)
-  float* send_d = nullptr;         // [D][PS]
-  float* recv_d = nullptr;         // [world][D][PS]
-  float* gather_tmp_d = nullptr;   // [D][world][PS] (records regrouped per system)
+  HipBuffer<float> send_d;         // [D][PS]
+  HipBuffer<float> recv_d;         // [world][D][PS]
+  HipBuffer<float> gather_tmp_d;   // [D][world][PS] (records regrouped per system)
   float* stats_d = nullptr;        // [D][STATS_STRIDE]
-  float* eps_d = nullptr;          // [n_eps_iters][K_local][T][C]
-  float* samples_d = nullptr;      // [D][K_local][T][C]
-  float* rows_d = nullptr;         // [num_blocks][bx * bz][rowStride]: the sampler's rows when they do not fit the LDS
-  float* fin_scratch_d = nullptr;  // [D][(2 T + 4) C]: smoothing buffer + sequence of the finalize kernels at long horizons
+  HipBuffer<float> eps_d;          // [n_eps_iters][K_local][T][C]
+  HipBuffer<float> samples_d;      // [D][K_local][T][C]
+  HipBuffer<float> rows_d;         // [num_blocks][bx * bz][rowStride]: the sampler's rows when they do not fit the LDS
+  HipBuffer<float> fin_scratch_d;  // [D][(2 T + 4) C]: smoothing buffer + sequence of the finalize kernels at long horizons
   bool rm_pipeline = false;        // Robust MPPI: ask the model for its role-pipelined rollout kernel (rows in HBM, bx = 64)
   bool rows_in_hbm = false;
   /* ColoredMPPI options (controllers/ColoredMPPI/colored_mppi_controller.cuh:18-22, 159-193): Tsallis weights and state leash */
   float tsallis_gamma = 0.0f, tsallis_r = 0.0f;
-  float* tsallis_weights_d = nullptr;  // [K_local]
-  float* tsallis_record_d = nullptr;   // [PS] K-sharded Tsallis: {sum w v | rho, sum w, sum w^2, 0} of this rank
+  HipBuffer<float> tsallis_weights_d;  // [K_local]
+  HipBuffer<float> tsallis_record_d;   // [PS] K-sharded Tsallis: {sum w v | rho, sum w, sum w^2, 0} of this rank
   /* reference-order reduction (mppi_set_reduction_mode, exact_reduce_kernels.hpp) */
   int reduction_mode = MPPI_REDUCTION_FUSED;
   int sum_strides = 32;                // GaussianParams::sum_strides (sampling_distributions/gaussian/gaussian.cuh:30)
-  float* exact_weights_d = nullptr;    // [D][K_local]
-  float* exact_inter_d = nullptr;      // [D][ceil(K_local / sum_strides)][T*C]
-  int exact_inter_cells = 0;
-  float* std_dev_time_d = nullptr;     // [D][T][C] time_specific_std_dev table
+  HipBuffer<float> exact_weights_d;    // [D][K_local]
+  HipBuffer<float> exact_inter_d;      // [D][ceil(K_local / sum_strides)][T*C]
+  HipBuffer<float> std_dev_time_d;     // [D][T][C] time_specific_std_dev table
   bool leash_active = false;
   int leash_jump = 1;
   std::vector<float> leash_dist;       // [S]
   float* history_d = nullptr;      // [2][C]
-  float* ctrl_in_d = nullptr;      // [D][T][C]
+  HipBuffer<float> ctrl_in_d;      // [D][T][C]
   float* ctrl_out_d = nullptr;     // [D][T][C]
   float* state_out_d = nullptr;    // [D][T][S]
   float* output_out_d = nullptr;   // [D][T][O]
   /* x0_d | mean_d | history_d are slices of ONE device block, ctrl_out_d | state_out_d | output_out_d | stats_d of
    * another, each mirrored in pinned host memory: mppi_compute_control hands its inputs over with one copy and takes its
    * results back with one copy and one synchronisation (single-system controllers; the others copy slice by slice) */
-  float* in_block_d = nullptr;
-  float* out_block_d = nullptr;
-  float* in_pin_h = nullptr;
-  float* out_pin_h = nullptr;
+  HipBuffer<float> in_block_d;
+  HipBuffer<float> out_block_d;
+  HipBuffer<float> in_pin_h;
+  HipBuffer<float> out_pin_h;
   /* low-latency hand-over of the single-system controllers (computeControlVanilla): host memory mapped into the device —
    * the first kernel reads the inputs from io_in, the finalize kernel writes the results to io_out and raises io_flags the
-   * host spins on (flag 0: control sequence + statistics out; flag 1: state / output trajectories out) */
-  float* io_in_h = nullptr;
-  float* io_in_dev = nullptr;
-  float* io_out_h = nullptr;
-  float* io_out_dev = nullptr;
-  unsigned* io_flags_h = nullptr;
-  unsigned* io_flags_dev = nullptr;
+   * host spins on (flag 0: control sequence + statistics out; flag 1: state / output trajectories out); .dev() is the
+   * device address of each */
+  HipBuffer<float> io_in_h;
+  HipBuffer<float> io_out_h;
+  HipBuffer<unsigned> io_flags_h;
   unsigned io_seq = 0;
   bool results_in_io = false;      // the last finalize pass wrote to io_out_h (low-latency path), not to out_block_d
   bool traj_pending = false;       // state_h / output of the last call are still being written by the finalize kernel
@@ -163,7 +166,7 @@ struct mppi_handle_s
   /* Round 5: the input block of the low-latency hand-over is DEVICE memory the host writes through the PCIe BAR
    * (hipExtMallocWithFlags(hipDeviceMallocFinegrained) on a large-BAR device: the allocation accepts CPU stores,
    * tools/ubench/bar_write.hip — {write 2 KB, launch, flag back} 8.3 us against 17.4 us with mapped host memory).  io_in_h and
-   * io_in_dev then are the same pointer; the host only ever WRITES it (write-combined, fenced before the launch).  With it
+   * io_in_h.dev() then are the same pointer; the host only ever WRITES it (write-combined, fenced before the launch).  With it
    * the Vanilla / Colored computeControl needs no ingest launch: the first rollout launch reads its mean, every rollout launch
    * and the finalize kernel their initial state and history, from the inbox (HBM, not PCIe).  MPPI_AMD_BAR_INBOX=0: mapped
    * host memory + ingest kernel as before. */
@@ -179,10 +182,8 @@ struct mppi_handle_s
    * launch as before. */
   bool split_finalize = false;
   bool side_pending = false;        // a trajectory phase is (possibly) in flight that h->stream has not been ordered behind
-  hipStream_t side_stream = nullptr;
-  hipEvent_t ev_side = nullptr;      // recorded behind every trajectory phase: what joinSideStream orders h->stream behind
-  float* carry_d = nullptr;         // [2][in_floats] + 2 x 2 words: the blocks' ready flags (FinalizeArgs::carry_ready_d)
-  float* fin_scratch2_d = nullptr;  // the trajectory phase's own smoothing-buffer block at long horizons (fin_scratch_d's twin)
+  HipBuffer<float> carry_d;         // [2][in_floats] + 2 x 2 words: the blocks' ready flags (FinalizeArgs::carry_ready_d)
+  HipBuffer<float> fin_scratch2_d;  // the trajectory phase's own smoothing-buffer block at long horizons (fin_scratch_d's twin)
   unsigned carry_seq[2] = { 0, 0 };  // hand-over sequence number of the call whose trajectory phase reads carry block i (0: none)
   const float* x0_src_d = nullptr;    // where rollout launches read the initial state from (nullptr: x0_d)
   const float* mean_src_d = nullptr;  // where the NEXT rollout launch reads its nominal control from (nullptr: mean_d; one-shot)
@@ -190,17 +191,15 @@ struct mppi_handle_s
    * (mppi_debug_host_stamps; tools/compute_control_host_timing.py): [0] inputs written, [1] ingest enqueued, [2] iterations
    * enqueued, [3] merge flushed, [4] finalize enqueued, [5] flag 0 seen, [6] results copied out */
   double host_stamps_us[8] = { 0 };
-  float* step_pin_h = nullptr;     // [S + C] host memory mapped into the device: [x | u] of a single model step
-  float* step_pin_dev = nullptr;   // its device address
+  HipBuffer<float> step_pin_h;     // [S + C] host memory mapped into the device: [x | u] of a single model step
   unsigned step_seq = 0;           // hand-over counter of the model-step flag (io_flags[8])
   size_t in_floats = 0, out_floats = 0;
   bool out_pin_fresh = false;      // out_pin_h holds the results (incl. stats) of the last finalize pass; reset by launches
   bool stats_h_fresh = false;      // stats_h IS the statistics of the last merge (parsed at a low-latency hand-over); reset by launches
-  float* step_x_d = nullptr;       // [S]
-  float* step_u_d = nullptr;       // [C]
-  int n_eps_iters = 0;
+  HipBuffer<float> step_x_d;       // [S + C]
+  float* step_u_d = nullptr;       // [C]: slice of step_x_d
+  int n_eps_iters = 0;             // iterations of injected noise eps_d holds (0: none)
   size_t noise_floats = 0;         // injected-noise floats per rollout (T*C, or C*(2T+2) spectrum entries when colored)
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
 
   /* host state (the reference's control_, control_history_, state_, nominal_* members) */
   std::vector<float> control_h, history_h, state_h, nominal_control_h, nominal_state_h, slide_scale_h;
@@ -225,30 +224,26 @@ struct mppi_handle_s
   std::vector<float> rm_nominal_state, rm_line_weights, rm_cand_states, rm_cand_costs, rm_cand_free_energy,
       nominal_history_h;
   std::vector<int> rm_cand_strides;
-  float* cand_states_d = nullptr;
-  float* cand_costs_d = nullptr;
-  int* cand_strides_d = nullptr;
-  int cand_capacity = 0;     // candidates * samples the cost buffers hold
-  int cand_capacity_nc = 0;  // candidates the state / stride buffers hold
+  HipBuffer<float> cand_states_d;   // [candidates][S]
+  HipBuffer<float> cand_costs_d;    // [candidates * samples]
+  HipBuffer<int> cand_strides_d;    // [candidates]
   /* the same three in host memory mapped into the device (low-latency hand-over: the candidate kernel reads its inputs and
    * writes its costs in place, the host waits on io_flags[9]): [states (nc * S) | strides (nc ints) | costs (nc * ns)] */
-  float* cand_io_h = nullptr;
-  float* cand_io_dev = nullptr;
+  HipBuffer<float> cand_io_h;
   unsigned cand_seq = 0;
 
   /* rocRAND host API (MPPI_NOISE_ROCRAND_HOST; librocrand.so loaded lazily): the reference's structure — a library
    * generator fills an eps buffer in HBM (curandGenerateNormal, sampling_distributions/gaussian/gaussian.cu:380-394) */
   void* rocrand_lib = nullptr;
   void* rocrand_gen = nullptr;
-  float* rocrand_eps_d = nullptr;  // [K_local][noise floats per rollout], refilled before every rollout launch
+  HipBuffer<float> rocrand_eps_d;  // [K_local][noise floats per rollout], refilled before every rollout launch
   /* RCCL (loaded lazily) */
   void* rccl_lib = nullptr;
   void* comm = nullptr;
 
   /* P2P mailbox exchange over xGMI (mppi_p2p_*): this rank's mailbox — records [2 parities][world][D * PS] followed by
    * flags [2][world] — lives in this GPU's memory and is written by the peers' postRecordsKernel */
-  float* mbox_d = nullptr;
-  size_t mbox_bytes = 0;
+  HipBuffer<float> mbox_d;
   bool mbox_uncached = false;
   float* peer_mbox[16] = { nullptr };
   bool peer_opened[16] = { false };  // hipIpcOpenMemHandle'd (to be closed)
@@ -257,6 +252,8 @@ struct mppi_handle_s
   unsigned xseq = 0;  // exchange sequence number: flags carry it, its parity selects the mailbox half
   size_t mbox_aux_off = 0;  // aux channel of the mailbox (Robust MPPI candidate costs), in 4-byte words from mbox_d
   unsigned aseq = 0;        // its own sequence number
+
+  ~mppi_handle_s();
 };
 
 struct RocrandApi
@@ -335,18 +332,12 @@ inline mppi_status ensureExactBuffers(mppi_handle h)
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (!h->samples_d)
-    HIP_TRY(h, hipMalloc((void**)&h->samples_d, sizeof(float) * (size_t)h->D * h->K_local * h->TC));
+    HIP_TRY(h, h->samples_d.alloc((size_t)h->D * h->K_local * h->TC));
   if (!h->exact_weights_d)
-    HIP_TRY(h, hipMalloc((void**)&h->exact_weights_d, sizeof(float) * (size_t)h->D * h->K_local));
-  const int cells = (h->K_local - 1) / h->sum_strides + 1;
-  if (!h->exact_inter_d || cells > h->exact_inter_cells)
-  {
-    if (h->exact_inter_d)
-      (void)hipFree(h->exact_inter_d);
-    h->exact_inter_d = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&h->exact_inter_d, sizeof(float) * (size_t)h->D * cells * h->TC));
-    h->exact_inter_cells = cells;
-  }
+    HIP_TRY(h, h->exact_weights_d.alloc((size_t)h->D * h->K_local));
+  const size_t inter = (size_t)h->D * ((h->K_local - 1) / h->sum_strides + 1) * h->TC;
+  if (inter > h->exact_inter_d.size())
+    HIP_TRY(h, h->exact_inter_d.alloc(inter));
   // the attribute belongs to (function, device): set per call — it is cheap — rather than once per process
   HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kernels::exactWeightsKernel),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kernels::EXACT_WEIGHTS_LDS_BYTES));

@@ -125,11 +125,11 @@ mppi_status mppi_choose_kernel(mppi_handle h, int num_evaluations, int* chosen_v
    * handle's merge needs its peers and is the same launch for both structures: there the rollout kernels alone are timed. */
   const bool whole_iterations = !exchangeActive(h) && !tsallisActive(h);
   PendingRecordsGuard guard{ h };
-  float* saved_d = nullptr;
+  HipBuffer<float> saved_d;
   const size_t mean_floats = (size_t)h->D * h->TC, stats_floats = (size_t)h->D * kernels::STATS_STRIDE;
   if (whole_iterations)
   {
-    HIP_TRY(h, hipMalloc((void**)&saved_d, sizeof(float) * (mean_floats + stats_floats)));
+    HIP_TRY(h, saved_d.alloc(mean_floats + stats_floats));
     (void)hipMemcpyAsync(saved_d, h->mean_d, sizeof(float) * mean_floats, hipMemcpyDeviceToDevice, h->stream);
     (void)hipMemcpyAsync(saved_d + mean_floats, h->stats_d, sizeof(float) * stats_floats, hipMemcpyDeviceToDevice, h->stream);
   }
@@ -140,8 +140,7 @@ mppi_status mppi_choose_kernel(mppi_handle h, int num_evaluations, int* chosen_v
     (void)hipMemcpyAsync(h->mean_d, saved_d, sizeof(float) * mean_floats, hipMemcpyDeviceToDevice, h->stream);
     (void)hipMemcpyAsync(h->stats_d, saved_d + mean_floats, sizeof(float) * stats_floats, hipMemcpyDeviceToDevice, h->stream);
     (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(saved_d);
-    saved_d = nullptr;
+    saved_d.reset();
   };
   for (int v = 0; v < 2; v++)
   {
@@ -195,6 +194,15 @@ mppi_status mppi_debug_host_stamps(mppi_handle h, double* out8)
   if (!out8)
     return fail(h, MPPI_ERR_INVALID_ARG, "null");
   std::copy(h->host_stamps_us, h->host_stamps_us + 8, out8);
+  return MPPI_OK;
+}
+
+mppi_status mppi_debug_live_allocations(int64_t* count, int64_t* bytes)
+{
+  if (!count || !bytes)
+    return MPPI_ERR_INVALID_ARG;
+  *count = liveAllocations().count;
+  *bytes = liveAllocations().bytes;
   return MPPI_OK;
 }
 

@@ -54,19 +54,6 @@ mppi_status mppi_model_step(mppi_handle h, float* x, float* u, float dt, int enf
 
 namespace
 {
-struct DevBuf
-{
-  float* p = nullptr;
-  ~DevBuf()
-  {
-    if (p)
-      (void)hipFree(p);
-  }
-  hipError_t alloc(size_t n)
-  {
-    return hipMalloc((void**)&p, n * sizeof(float));
-  }
-};
 mppi_status opFail(const char* what, hipError_t e)
 {
   g_create_error = std::string(what) + ": " + hipGetErrorString(e);
@@ -100,13 +87,13 @@ mppi_status mppi_norm_exp(float* costs, int K, float lambda_inv, float baseline,
   if (!costs || K <= 0)
     return MPPI_ERR_INVALID_ARG;
   MPPI_TRY(opDevice(device));
-  DevBuf d;
+  HipBuffer<float> d;
   OP_TRY(d.alloc(K));
-  OP_TRY(hipMemcpy(d.p, costs, sizeof(float) * K, hipMemcpyHostToDevice));
+  OP_TRY(hipMemcpy(d, costs, sizeof(float) * K, hipMemcpyHostToDevice));
   // reference: norm_exp_kernel_parallelization_ = 64 (controller.cuh:64) -> grid ceil(K/64) x 64
-  hipLaunchKernelGGL(kernels::normExpKernel, dim3((K + 63) / 64), dim3(64), 0, 0, K, d.p, lambda_inv, baseline);
+  hipLaunchKernelGGL(kernels::normExpKernel, dim3((K + 63) / 64), dim3(64), 0, 0, K, d, lambda_inv, baseline);
   OP_TRY(hipGetLastError());
-  OP_TRY(hipMemcpy(costs, d.p, sizeof(float) * K, hipMemcpyDeviceToHost));
+  OP_TRY(hipMemcpy(costs, d, sizeof(float) * K, hipMemcpyDeviceToHost));
   return MPPI_OK;
 }
 
@@ -115,15 +102,15 @@ mppi_status mppi_compute_weights(float* costs, int K, float lambda_inv, float* o
   if (!costs || !out2 || K <= 0)
     return MPPI_ERR_INVALID_ARG;
   MPPI_TRY(opDevice(device));
-  DevBuf d, o;
+  HipBuffer<float> d, o;
   OP_TRY(d.alloc(K));
   OP_TRY(o.alloc(2));
-  OP_TRY(hipMemcpy(d.p, costs, sizeof(float) * K, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(kernels::computeWeightsKernel, dim3(1), dim3(kernels::COMBINE_THREADS), 0, 0, K, d.p, lambda_inv,
-                     o.p);
+  OP_TRY(hipMemcpy(d, costs, sizeof(float) * K, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kernels::computeWeightsKernel, dim3(1), dim3(kernels::COMBINE_THREADS), 0, 0, K, d, lambda_inv,
+                     o);
   OP_TRY(hipGetLastError());
-  OP_TRY(hipMemcpy(costs, d.p, sizeof(float) * K, hipMemcpyDeviceToHost));
-  OP_TRY(hipMemcpy(out2, o.p, sizeof(float) * 2, hipMemcpyDeviceToHost));
+  OP_TRY(hipMemcpy(costs, d, sizeof(float) * K, hipMemcpyDeviceToHost));
+  OP_TRY(hipMemcpy(out2, o, sizeof(float) * 2, hipMemcpyDeviceToHost));
   return MPPI_OK;
 }
 
@@ -133,19 +120,19 @@ mppi_status mppi_weighted_reduction(const float* weights, const float* v, float 
   if (!weights || !v || !u_out || K <= 0 || T <= 0 || C <= 0)
     return MPPI_ERR_INVALID_ARG;
   MPPI_TRY(opDevice(device));
-  DevBuf w, vd, u;
+  HipBuffer<float> w, vd, u;
   const size_t TC = (size_t)T * C;
   OP_TRY(w.alloc(K));
   OP_TRY(vd.alloc((size_t)K * TC));
   OP_TRY(u.alloc(TC));
-  OP_TRY(hipMemcpy(w.p, weights, sizeof(float) * K, hipMemcpyHostToDevice));
-  OP_TRY(hipMemcpy(vd.p, v, sizeof(float) * K * TC, hipMemcpyHostToDevice));
-  OP_TRY(hipMemset(u.p, 0, sizeof(float) * TC));
+  OP_TRY(hipMemcpy(w, weights, sizeof(float) * K, hipMemcpyHostToDevice));
+  OP_TRY(hipMemcpy(vd, v, sizeof(float) * K * TC, hipMemcpyHostToDevice));
+  OP_TRY(hipMemset(u, 0, sizeof(float) * TC));
   const int per_block = 32;
-  hipLaunchKernelGGL(kernels::weightedReductionKernel, dim3((K + per_block - 1) / per_block), dim3(256), 0, 0, w.p,
-                     vd.p, u.p, normalizer, (int)TC, K, per_block);
+  hipLaunchKernelGGL(kernels::weightedReductionKernel, dim3((K + per_block - 1) / per_block), dim3(256), 0, 0, w,
+                     vd, u, normalizer, (int)TC, K, per_block);
   OP_TRY(hipGetLastError());
-  OP_TRY(hipMemcpy(u_out, u.p, sizeof(float) * TC, hipMemcpyDeviceToHost));
+  OP_TRY(hipMemcpy(u_out, u, sizeof(float) * TC, hipMemcpyDeviceToHost));
   return MPPI_OK;
 }
 
@@ -154,25 +141,25 @@ mppi_status mppi_compute_weights_reference_order(float* costs, int K, float lamb
   if (!costs || !stats8 || K <= 0 || !(lambda > 0.0f))
     return MPPI_ERR_INVALID_ARG;
   MPPI_TRY(opDevice(device));
-  DevBuf c, w, st;
+  HipBuffer<float> c, w, st;
   OP_TRY(c.alloc(K));
   OP_TRY(w.alloc(K));
   OP_TRY(st.alloc(kernels::STATS_STRIDE));
-  OP_TRY(hipMemcpy(c.p, costs, sizeof(float) * K, hipMemcpyHostToDevice));
+  OP_TRY(hipMemcpy(c, costs, sizeof(float) * K, hipMemcpyHostToDevice));
   OP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernels::exactWeightsKernel),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kernels::EXACT_WEIGHTS_LDS_BYTES));
   kernels::ExactWeightsArgs a{};
   a.num_rollouts = K;
-  a.costs_d = c.p;
-  a.weights_d = w.p;
-  a.stats_out_d = st.p;
+  a.costs_d = c;
+  a.weights_d = w;
+  a.stats_out_d = st;
   a.lambda = lambda;
   a.lambda_inv = (float)(1.0 / (double)lambda);
   hipLaunchKernelGGL(kernels::exactWeightsKernel, dim3(1), dim3(kernels::COMBINE_THREADS), kernels::EXACT_WEIGHTS_LDS_BYTES,
                      0, a);
   OP_TRY(hipGetLastError());
-  OP_TRY(hipMemcpy(costs, w.p, sizeof(float) * K, hipMemcpyDeviceToHost));
-  OP_TRY(hipMemcpy(stats8, st.p, sizeof(float) * kernels::STATS_STRIDE, hipMemcpyDeviceToHost));
+  OP_TRY(hipMemcpy(costs, w, sizeof(float) * K, hipMemcpyDeviceToHost));
+  OP_TRY(hipMemcpy(stats8, st, sizeof(float) * kernels::STATS_STRIDE, hipMemcpyDeviceToHost));
   return MPPI_OK;
 }
 
@@ -182,7 +169,7 @@ mppi_status mppi_weighted_reduction_reference_order(const float* weights, const 
   if (!weights || !v || !u_out || K <= 0 || T <= 0 || C <= 0 || sum_stride <= 0)
     return MPPI_ERR_INVALID_ARG;
   MPPI_TRY(opDevice(device));
-  DevBuf w, vd, u, st, inter;
+  HipBuffer<float> w, vd, u, st, inter;
   const int TC = T * C;
   const int cells = (K - 1) / sum_stride + 1;
   OP_TRY(w.alloc(K));
@@ -191,19 +178,19 @@ mppi_status mppi_weighted_reduction_reference_order(const float* weights, const 
   OP_TRY(st.alloc(kernels::STATS_STRIDE));
   OP_TRY(inter.alloc((size_t)cells * TC));
   float sth[kernels::STATS_STRIDE] = { 0.0f, normalizer };
-  OP_TRY(hipMemcpy(w.p, weights, sizeof(float) * K, hipMemcpyHostToDevice));
-  OP_TRY(hipMemcpy(vd.p, v, sizeof(float) * (size_t)K * TC, hipMemcpyHostToDevice));
-  OP_TRY(hipMemcpy(st.p, sth, sizeof(sth), hipMemcpyHostToDevice));
+  OP_TRY(hipMemcpy(w, weights, sizeof(float) * K, hipMemcpyHostToDevice));
+  OP_TRY(hipMemcpy(vd, v, sizeof(float) * (size_t)K * TC, hipMemcpyHostToDevice));
+  OP_TRY(hipMemcpy(st, sth, sizeof(sth), hipMemcpyHostToDevice));
   const dim3 grid((TC + 63) / 64, (cells + kernels::COMBINE_THREADS / 64 - 1) / (kernels::COMBINE_THREADS / 64), 1);
   if (fma)
-    hipLaunchKernelGGL(kernels::exactReductionCellsKernel<1>, grid, dim3(kernels::COMBINE_THREADS), 0, 0, w.p, vd.p, st.p, TC,
-                       K, sum_stride, cells, inter.p);
+    hipLaunchKernelGGL(kernels::exactReductionCellsKernel<1>, grid, dim3(kernels::COMBINE_THREADS), 0, 0, w, vd, st, TC,
+                       K, sum_stride, cells, inter);
   else
-    hipLaunchKernelGGL(kernels::exactReductionCellsKernel<0>, grid, dim3(kernels::COMBINE_THREADS), 0, 0, w.p, vd.p, st.p, TC,
-                       K, sum_stride, cells, inter.p);
-  hipLaunchKernelGGL(kernels::exactReductionFinalKernel, dim3((TC + 63) / 64, 1), dim3(64), 0, 0, inter.p, TC, cells, u.p);
+    hipLaunchKernelGGL(kernels::exactReductionCellsKernel<0>, grid, dim3(kernels::COMBINE_THREADS), 0, 0, w, vd, st, TC,
+                       K, sum_stride, cells, inter);
+  hipLaunchKernelGGL(kernels::exactReductionFinalKernel, dim3((TC + 63) / 64, 1), dim3(64), 0, 0, inter, TC, cells, u);
   OP_TRY(hipGetLastError());
-  OP_TRY(hipMemcpy(u_out, u.p, sizeof(float) * TC, hipMemcpyDeviceToHost));
+  OP_TRY(hipMemcpy(u_out, u, sizeof(float) * TC, hipMemcpyDeviceToHost));
   return MPPI_OK;
 }
 
@@ -229,11 +216,11 @@ mppi_status mppi_philox_normal(uint64_t seed, uint32_t generation, int K, int T,
     return MPPI_ERR_INVALID_ARG;
   MPPI_TRY(opDevice(device));
   const size_t n = (size_t)(k_end - k_begin) * T * C;
-  DevBuf d;
+  HipBuffer<float> d;
   OP_TRY(d.alloc(n));
-  hipLaunchKernelGGL(philoxNormalKernel, dim3(256), dim3(256), 0, 0, seed, generation, T * C, k_begin, k_end, d.p);
+  hipLaunchKernelGGL(philoxNormalKernel, dim3(256), dim3(256), 0, 0, seed, generation, T * C, k_begin, k_end, d);
   OP_TRY(hipGetLastError());
-  OP_TRY(hipMemcpy(eps_out, d.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+  OP_TRY(hipMemcpy(eps_out, d, sizeof(float) * n, hipMemcpyDeviceToHost));
   return MPPI_OK;
 }
 
@@ -300,16 +287,16 @@ template <int NC>
 static mppi_status texture2dQuery(const float* data, int width, int height, const mppi_texture2d_params* p,
                                   const float* points, int n, int frame, float* out)
 {
-  DevBuf dd, dp, dout;
+  HipBuffer<float> dd, dp, dout;
   const size_t texels = (size_t)width * height * NC;
   OP_TRY(dd.alloc(texels));
   OP_TRY(dp.alloc((size_t)3 * n));
   OP_TRY(dout.alloc((size_t)n * NC));
-  OP_TRY(hipMemcpy(dd.p, data, sizeof(float) * texels, hipMemcpyHostToDevice));
-  OP_TRY(hipMemcpy(dp.p, points, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+  OP_TRY(hipMemcpy(dd, data, sizeof(float) * texels, hipMemcpyHostToDevice));
+  OP_TRY(hipMemcpy(dp, points, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
   mppi::texture::TwoDTextureHelper<1, NC> helper;
   mppi::texture::TextureParams2D& t = helper.textures_[0];
-  t.data = dd.p;
+  t.data = dd;
   t.width = width;
   t.height = height;
   t.use = 1;
@@ -320,9 +307,9 @@ static mppi_status texture2dQuery(const float* data, int width, int height, cons
   memcpy(t.origin, p->origin, sizeof(t.origin));
   memcpy(t.rotations, p->rotations, sizeof(t.rotations));
   memcpy(t.resolution, p->resolution, sizeof(t.resolution));
-  hipLaunchKernelGGL((texture2dQueryKernel<NC>), dim3((n + 255) / 256), dim3(256), 0, 0, helper, dp.p, n, frame, dout.p);
+  hipLaunchKernelGGL((texture2dQueryKernel<NC>), dim3((n + 255) / 256), dim3(256), 0, 0, helper, dp, n, frame, dout);
   OP_TRY(hipGetLastError());
-  OP_TRY(hipMemcpy(out, dout.p, sizeof(float) * n * NC, hipMemcpyDeviceToHost));
+  OP_TRY(hipMemcpy(out, dout, sizeof(float) * n * NC, hipMemcpyDeviceToHost));
   return MPPI_OK;
 }
 }  // extern "C++"
@@ -350,13 +337,13 @@ mppi_status mppi_measure_launch_boundary(int device, int n, float* us_per_launch
   if (n <= 0 || !us_per_launch)
     return MPPI_ERR_INVALID_ARG;
   MPPI_TRY(opDevice(device));
-  hipStream_t s = nullptr;
-  hipEvent_t a = nullptr, b = nullptr;
-  hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  HipStream s;
+  HipEvent a, b;
+  hipError_t e = s.create(hipStreamNonBlocking);
   if (e == hipSuccess)
-    e = hipEventCreate(&a);
+    e = a.create(hipEventDefault);
   if (e == hipSuccess)
-    e = hipEventCreate(&b);
+    e = b.create(hipEventDefault);
   // the launches are replayed from a graph: enqueued one by one the host is the bottleneck (~3 us per launch), which is not
   // what separates two kernels of an iteration whose launches were queued long before the first one finished
   float ms = 0.0f;
@@ -390,12 +377,6 @@ mppi_status mppi_measure_launch_boundary(int device, int n, float* us_per_launch
     (void)hipGraphExecDestroy(exec);
   if (graph)
     (void)hipGraphDestroy(graph);
-  if (a)
-    (void)hipEventDestroy(a);
-  if (b)
-    (void)hipEventDestroy(b);
-  if (s)
-    (void)hipStreamDestroy(s);
   if (e != hipSuccess)
     return opFail("mppi_measure_launch_boundary", e);
   *us_per_launch = ms * 1e3f / (float)n;
@@ -432,21 +413,21 @@ mppi_status mppi_measure_issue_interval(int device, float* ns_per_instruction)
   if (!ns_per_instruction)
     return MPPI_ERR_INVALID_ARG;
   MPPI_TRY(opDevice(device));
-  hipStream_t s = nullptr;
-  hipEvent_t a = nullptr, b = nullptr;
-  hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  HipStream s;
+  HipEvent a, b;
+  hipError_t e = s.create(hipStreamNonBlocking);
   if (e == hipSuccess)
-    e = hipEventCreate(&a);
+    e = a.create(hipEventDefault);
   if (e == hipSuccess)
-    e = hipEventCreate(&b);
+    e = b.create(hipEventDefault);
   // two chain lengths, differenced: launch ramp, loop overhead and the tail fall out.  The probes follow a ~10 ms warm-up
   // launch on the same stream with no host synchronisation in between: short kernels after an idle gap run below the
   // sustained clock (first version of this probe: 3.4 ns instead of 1.9).
   constexpr int CHAIN = 256;
   const int trips[2] = { 256, 1280 };
-  hipEvent_t c = nullptr;
+  HipEvent c;
   if (e == hipSuccess)
-    e = hipEventCreate(&c);
+    e = c.create(hipEventDefault);
   float best = 1e30f;
   for (int rep = 0; rep < 3 && e == hipSuccess; rep++)
   {
@@ -468,14 +449,6 @@ mppi_status mppi_measure_issue_interval(int device, float* ns_per_instruction)
     if (e == hipSuccess && t1 - t0 < best)
       best = t1 - t0;
   }
-  if (c)
-    (void)hipEventDestroy(c);
-  if (a)
-    (void)hipEventDestroy(a);
-  if (b)
-    (void)hipEventDestroy(b);
-  if (s)
-    (void)hipStreamDestroy(s);
   if (e != hipSuccess)
     return opFail("mppi_measure_issue_interval", e);
   *ns_per_instruction = best * 1e6f / (float)((trips[1] - trips[0]) * CHAIN);
@@ -487,12 +460,12 @@ mppi_status mppi_det_eval(int func, const float* x, float* y, int n, int device)
   if (!x || !y || n <= 0)
     return MPPI_ERR_INVALID_ARG;
   MPPI_TRY(opDevice(device));
-  DevBuf dx, dy;
+  HipBuffer<float> dx, dy;
   OP_TRY(dx.alloc(n));
   OP_TRY(dy.alloc(n));
-  OP_TRY(hipMemcpy(dx.p, x, sizeof(float) * n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(detEvalKernel, dim3(256), dim3(256), 0, 0, func, dx.p, dy.p, n);
+  OP_TRY(hipMemcpy(dx, x, sizeof(float) * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(detEvalKernel, dim3(256), dim3(256), 0, 0, func, dx, dy, n);
   OP_TRY(hipGetLastError());
-  OP_TRY(hipMemcpy(y, dy.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+  OP_TRY(hipMemcpy(y, dy, sizeof(float) * n, hipMemcpyDeviceToHost));
   return MPPI_OK;
 }
