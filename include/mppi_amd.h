@@ -198,6 +198,21 @@ mppi_status mppi_register_model_checked(const char* name, int sampler_kind, mppi
                                         unsigned flags);
 /** dlopen()s a library whose static initialisers call mppi_register_model; the library stays loaded */
 mppi_status mppi_load_plugin(const char* path);
+/**
+ * What a registered instantiation offers, without a handle and without a device: its block shapes and which kernel forms
+ * exist for it (the table mppi_create chooses from).  shapes[capacity][4] receives (bx, by, bz, replicated) per registered
+ * shape, the replicated-lane (MFMA / four-lane) ones first with replicated = 1; *num_shapes is always the full count, so a
+ * call with capacity 0 asks for the size.  *caps: MPPI_MODEL_CAP_* flags.  MPPI_ERR_UNKNOWN_MODEL when (name, sampler_kind)
+ * is not registered.  shapes, num_shapes and caps may each be NULL.
+ */
+#define MPPI_MODEL_CAP_PIPELINE 1u       /* rolloutPipelineKernel (one lane per rollout; (64, 1, bz), and (32, 1, 2) folded) */
+#define MPPI_MODEL_CAP_RMPPI 2u          /* Robust MPPI (rolloutRMPPIKernel) */
+#define MPPI_MODEL_CAP_RMPPI_PIPELINE 4u /* rolloutRMPPIPipelineKernel */
+#define MPPI_MODEL_CAP_ROWS_IN_HBM 8u    /* the sampler's rows may live in HBM (long horizons, MPPI_AMD_ROWS_IN_HBM=1) */
+#define MPPI_MODEL_CAP_STREAMED_MERGE 16u /* the pipeline's sampler waves can merge the previous launch's block records */
+#define MPPI_MODEL_CAP_PIPELINE_FOLD 32u /* Tube's two systems folded into the lanes of a wave, shape (32, 1, 2) */
+mppi_status mppi_describe_model(const char* name, int sampler_kind, int* shapes, int capacity, int* num_shapes,
+                                unsigned* caps);
 
 /* ---------------------------------------------------------------- lifecycle -------------------------------------- */
 /** Controller constructor + GPUSetup + allocateCUDAMemory (controllers/controller.cuh:160-216, 269-277, 931-992) */
@@ -218,6 +233,31 @@ mppi_status mppi_get_local_rollouts(mppi_handle h, int* k_local, int* k_offset);
  * Either pointer may be NULL.
  */
 mppi_status mppi_get_launch_counts(mppi_handle h, unsigned long long* rollout_launches, unsigned long long* merge_launches);
+/** the rollout kernels a handle can launch (mppi_launch_info::family) */
+typedef enum mppi_kernel_family
+{
+  MPPI_FAMILY_NONE = 0,          /* no rollout launch yet */
+  MPPI_FAMILY_FUSED = 1,         /* rolloutKernel (engine/rollout_kernel.hpp) */
+  MPPI_FAMILY_FUSED_REP = 2,     /* rolloutKernel on the replicated-lane (MFMA / four-lane) form of the dynamics */
+  MPPI_FAMILY_PIPELINE = 3,      /* rolloutPipelineKernel, one lane per rollout (engine/rollout_pipeline_kernel.hpp) */
+  MPPI_FAMILY_PIPELINE_FOLD = 4, /* rolloutPipelineKernel with Tube's two systems folded into the lanes of a wave */
+  MPPI_FAMILY_PIPELINE_REP = 5,  /* rolloutPipelineRepKernel (replicated-lane dynamics) */
+  MPPI_FAMILY_RMPPI = 6,         /* rolloutRMPPIKernel (engine/rmppi_kernels.hpp) */
+  MPPI_FAMILY_RMPPI_PIPELINE = 7 /* rolloutRMPPIPipelineKernel (engine/rmppi_pipeline_kernel.hpp) */
+} mppi_kernel_family;
+typedef struct mppi_launch_info
+{
+  int family;                    /* mppi_kernel_family */
+  int block_x, block_y, block_z; /* the registered block shape the launch was dispatched for */
+  int rows_in_hbm;               /* the sampler's rows lived in HBM */
+  int streamed_merge;            /* the sampler waves merged the previous launch's block records (one-system pipeline) */
+} mppi_launch_info;
+/**
+ * The most recent rollout launch of this handle, as the launch path recorded it when it dispatched the kernel (mppi_create,
+ * mppi_set_model_blob and the horizon can each move a handle off the form it was asked for; this reports what ran).
+ * MPPI_ERR_STATE before the first launch.
+ */
+mppi_status mppi_get_launch_info(mppi_handle h, mppi_launch_info* out);
 
 /* ---------------------------------------------------------------- parameters ------------------------------------- */
 /** Dynamics::setParams + paramsToDevice (dynamics/dynamics.cu:3-17); pod = the model's *_dynamics_params (mppi_amd/model_params.h) */

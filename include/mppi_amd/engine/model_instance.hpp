@@ -86,10 +86,21 @@ struct SamplerLaunchState
   int independent_noise;  // != 0: use_same_noise_for_all_distributions off (every distribution its own stream / eps slab)
 };
 
+/** what the most recent rollout launch of a model object ran (mppi_get_launch_info): written by the dispatch itself, at the
+ *  point where it has picked the kernel and the launch went out, so the query never recomputes the choice */
+struct LaunchRecord
+{
+  int family = MPPI_FAMILY_NONE;  ///< mppi_kernel_family
+  int bx = 0, by = 0, bz = 0;     ///< the registered block shape the launch was dispatched for
+  bool rows_in_hbm = false;       ///< the sampler's rows in HBM (setGlobalRows)
+  bool streamed_merge = false;    ///< the sampler waves merged the previous launch's block records (STREAM_MERGE form)
+};
+
 struct ModelBase
 {
   int S = 0, C = 0, O = 0;
   int default_bx = 64, default_by = 1;
+  LaunchRecord last_launch;
   virtual ~ModelBase() = default;
   virtual mppi_status setDynamicsParams(const void* pod, size_t n) = 0;
   virtual mppi_status setCostParams(const void* pod, size_t n) = 0;
@@ -244,6 +255,15 @@ struct ModelBase
   /** x <- one model step (optionally after enforceConstraints on u), one block (1, by, 1) */
   virtual mppi_status launchModelStep(float* x_d, float* u_d, float dt, int enforce, hipStream_t stream,
                                       std::string& err) = 0;
+  /** the replicated-lane (MFMA / four-lane) block shapes among listShapes(), as (bx, by, bz) triples, flattened */
+  virtual void listReplicatedLaneShapes(std::vector<int>& out) const
+  {
+  }
+  /** the role-pipelined Robust MPPI kernel (rmppi_pipeline_kernel.hpp) is instantiated for this model */
+  virtual bool supportsRMPPIPipeline() const
+  {
+    return false;
+  }
 };
 
 /** fingerprint of the structures a model translation unit and libmppi_amd.so exchange (mppi_register_model refuses a
@@ -252,8 +272,9 @@ struct ModelBase
  *  swapped at equal size — changes sizeof() cannot see (a stale plugin would dispatch to the wrong vtable slot).
  *  3: rows-in-HBM arguments; 4: release-flag arguments of the finalize kernels (both round 3); 5: supportsStreamedMerge (round 4);
  *  6: FinalizeArgs::phases / carry block of the split hand-over (round 5); 7: undeclaredBarrierFreePlugins; 8: the transposed
- *  record copy (RolloutArgs) and supportsMergeControl / launchMergeControl (both round 6). */
-#define MPPI_ENGINE_ABI_VERSION 8
+ *  record copy (RolloutArgs) and supportsMergeControl / launchMergeControl (both round 6); 9: LaunchRecord,
+ *  listReplicatedLaneShapes / supportsRMPPIPipeline (the launch and model introspection of mppi_amd.h). */
+#define MPPI_ENGINE_ABI_VERSION 9
 
 constexpr int engineAbiFingerprint()
 {
@@ -714,15 +735,20 @@ struct ModelT : ModelBase
         return MPPI_ERR_STATE;
       }
       prepSampler(s);
+      auto noted = [&](int family, mppi_status st) {
+        if (st == MPPI_OK)
+          last_launch = LaunchRecord{family, bx, 1, 2, smp.rows_global_d_ != nullptr, false};
+        return st;
+      };
       if constexpr (rmppiHasPipeline())
       {
         if (pipeline && bx == 64 && rmppiPipelineUsable())
-          return launchRMPPIPipeline(a, stream, err);
+          return noted(MPPI_FAMILY_RMPPI_PIPELINE, launchRMPPIPipeline(a, stream, err));
       }
       if (bx == 64)
-        return launchRMPPIShape<64>(a, stream, err);
+        return noted(MPPI_FAMILY_RMPPI, launchRMPPIShape<64>(a, stream, err));
       if (bx == 32)  // horizons whose sample rows for 64 rollouts x 2 systems do not fit the LDS
-        return launchRMPPIShape<32>(a, stream, err);
+        return noted(MPPI_FAMILY_RMPPI, launchRMPPIShape<32>(a, stream, err));
       err = "Robust MPPI rollout kernel is instantiated for 64 or 32 rollouts per block";
       return MPPI_ERR_LAUNCH_SHAPE;
     }
@@ -732,6 +758,10 @@ struct ModelT : ModelBase
   bool supportsPipeline() const override
   {
     return PIPELINE;
+  }
+  bool supportsRMPPIPipeline() const override
+  {
+    return rmppiHasPipeline();
   }
   /** does the instantiation ask for role-separated kernels (the one-lane pipeline, or the replicated-lane one), and do the
    *  classes those kernels would run say that their per-step methods hold no block barrier? */
@@ -1435,6 +1465,10 @@ struct ModelT : ModelBase
     appendShapes(FAST_SHAPES{}, out);  // the MFMA shapes first: preferred at equal rollouts per block
     appendShapes(SHAPES{}, out);
   }
+  void listReplicatedLaneShapes(std::vector<int>& out) const override
+  {
+    appendShapes(FAST_SHAPES{}, out);
+  }
 
   void prepSampler(const SamplerLaunchState& s)
   {
@@ -1603,20 +1637,25 @@ struct ModelT : ModelBase
         return MPPI_ERR_LAUNCH_SHAPE;
       }
     }
+    auto noted = [&](int family, mppi_status st) {
+      if (st == MPPI_OK)
+        last_launch = LaunchRecord{family, bx, by, bz, smp.rows_global_d_ != nullptr, args.prev_records_d != nullptr};
+      return st;
+    };
     if (pipeline && supportsPipelineRep(bx, by, bz))
-      return launchPipelineRep(args, stream, err);
+      return noted(MPPI_FAMILY_PIPELINE_REP, launchPipelineRep(args, stream, err));
     if (pipeline && supportsPipelineFold(bx, by, bz))
-      return launchPipeline<2, true>(args, stream, err);
+      return noted(MPPI_FAMILY_PIPELINE_FOLD, launchPipeline<2, true>(args, stream, err));
     if (pipeline)
-      return bz == 1 ? launchPipeline<1>(args, stream, err) : launchPipeline<2>(args, stream, err);
+      return noted(MPPI_FAMILY_PIPELINE, bz == 1 ? launchPipeline<1>(args, stream, err) : launchPipeline<2>(args, stream, err));
     if constexpr (!std::is_void<DYN_FAST_T>::value)
     {
       bool handled = false;
       mppi_status st = dispatchFast(FAST_SHAPES{}, bx, by, bz, args, stream, err, handled);
       if (handled)
-        return st;
+        return noted(MPPI_FAMILY_FUSED_REP, st);
     }
-    return dispatch(SHAPES{}, bx, by, bz, args, stream, err);
+    return noted(MPPI_FAMILY_FUSED, dispatch(SHAPES{}, bx, by, bz, args, stream, err));
   }
 
   mppi_status launchFinalize(int D, const kernels::FinalizeArgs& a, hipStream_t stream, std::string& err) override

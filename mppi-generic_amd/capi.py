@@ -62,6 +62,11 @@ class MppiStats(C.Structure):
     _fields_ = [("real_sys", MppiSystemStats), ("nominal_sys", MppiSystemStats), ("nominal_state_used", C.c_int)]
 
 
+class MppiLaunchInfo(C.Structure):
+    _fields_ = [("family", C.c_int), ("block_x", C.c_int), ("block_y", C.c_int), ("block_z", C.c_int), ("rows_in_hbm", C.c_int),
+                ("streamed_merge", C.c_int)]
+
+
 # every symbol include/mppi_amd.h declares: name -> (restype, argtypes)
 H = C.c_void_p
 SIGNATURES = {
@@ -73,12 +78,15 @@ SIGNATURES = {
     "mppi_register_model": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_int]),
     "mppi_register_model_checked": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_int, C.c_uint]),
     "mppi_load_plugin": (C.c_int, [C.c_char_p]),
+    "mppi_describe_model": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                      C.POINTER(C.c_uint)]),
     "mppi_create": (C.c_int, [C.POINTER(MppiConfig), C.POINTER(H)]),
     "mppi_destroy": (None, [H]),
     "mppi_last_error": (C.c_char_p, [H]),
     "mppi_get_dims": (C.c_int, [H] + [C.POINTER(C.c_int)] * 4),
     "mppi_get_local_rollouts": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mppi_get_launch_counts": (C.c_int, [H, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "mppi_get_launch_info": (C.c_int, [H, C.POINTER(MppiLaunchInfo)]),
     "mppi_debug_host_stamps": (C.c_int, [H, C.POINTER(C.c_double)]),
     "mppi_debug_live_allocations": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mppi_set_dynamics_params": (C.c_int, [H, C.c_void_p, C.c_size_t]),

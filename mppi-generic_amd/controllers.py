@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import MppiConfig, MppiGaussianParams, MppiStats, load_library
+from .capi import MppiConfig, MppiGaussianParams, MppiLaunchInfo, MppiStats, load_library
 
 MPPI_CONTROLLER_VANILLA = 0
 MPPI_CONTROLLER_TUBE = 1
@@ -307,6 +307,15 @@ class MPPIController:
         r, g = C.c_ulonglong(), C.c_ulonglong()
         self._check(self._lib.mppi_get_launch_counts(self._h, C.byref(r), C.byref(g)))
         return r.value, g.value
+
+    def getLaunchInfo(self):
+        """the most recent rollout launch as the launch path recorded it (mppi_get_launch_info): dict with "family" (a
+        KERNEL_FAMILIES name), "block" (bx, by, bz), "rows_in_hbm" and "streamed_merge"; MPPIError(MPPI_ERR_STATE) before the
+        first launch"""
+        info = MppiLaunchInfo()
+        self._check(self._lib.mppi_get_launch_info(self._h, C.byref(info)))
+        return {"family": KERNEL_FAMILIES[info.family], "block": (info.block_x, info.block_y, info.block_z),
+                "rows_in_hbm": bool(info.rows_in_hbm), "streamed_merge": bool(info.streamed_merge)}
 
     # -- plumbing --
     def _check(self, st):
@@ -659,6 +668,39 @@ class TubeMPPIController(MPPIController):
         x = np.empty((self.num_timesteps, self.STATE_DIM), np.float32)
         self._check(self._lib.mppi_get_nominal_state_seq(self._h, x))
         return x
+
+
+# ---- introspection --------------------------------------------------------------------------------------------------
+# mppi_kernel_family (include/mppi_amd.h), by value
+KERNEL_FAMILIES = ("none", "fused", "fused_rep", "pipeline", "pipeline_fold", "pipeline_rep", "rmppi", "rmppi_pipeline")
+MPPI_SAMPLER_GAUSSIAN = 0
+MPPI_SAMPLER_COLORED = 1
+_MODEL_CAPS = (("pipeline", 1), ("rmppi", 2), ("rmppi_pipeline", 4), ("rows_in_hbm", 8), ("streamed_merge", 16),
+               ("pipeline_fold", 32))
+
+
+def list_models():
+    """names of the registered instantiations (mppi_list_models)"""
+    return [n for n in load_library().mppi_list_models().decode().split("\n") if n]
+
+
+def describe_model(name, sampler_kind=MPPI_SAMPLER_GAUSSIAN):
+    """what a registered (model, sampler) instantiation offers, without a device (mppi_describe_model): dict with "shapes"
+    (every registered (bx, by, bz)), "replicated_lane_shapes" (those that run the replicated-lane dynamics form) and one bool
+    per capability ("pipeline", "rmppi", "rmppi_pipeline", "rows_in_hbm", "streamed_merge", "pipeline_fold"); None when the
+    model has no instantiation for that sampler"""
+    lib = load_library()
+    n, caps = C.c_int(), C.c_uint()
+    st = lib.mppi_describe_model(name.encode(), sampler_kind, None, 0, C.byref(n), C.byref(caps))
+    if st == 2:  # MPPI_ERR_UNKNOWN_MODEL
+        return None
+    _op_check(lib, st)
+    buf = (C.c_int * (4 * n.value))()
+    _op_check(lib, lib.mppi_describe_model(name.encode(), sampler_kind, buf, n.value, C.byref(n), C.byref(caps)))
+    rows = [tuple(buf[4 * i:4 * i + 4]) for i in range(n.value)]
+    d = {"shapes": [r[:3] for r in rows], "replicated_lane_shapes": [r[:3] for r in rows if r[3]]}
+    d.update({k: bool(caps.value & bit) for k, bit in _MODEL_CAPS})
+    return d
 
 
 # ---- kernel-level operators -----------------------------------------------------------------------------------------

@@ -303,7 +303,7 @@ def _robust_pair(cfg, thr, reference_order, nc=9, ns=32, **kw):
     return eng, orc, po.RobustOracle(orc, thr, nc, ns)
 
 
-def _robust_two_cycles(cfg, thr, reference_order, x_real, require_finite_candidates=False, **kw):
+def _robust_two_cycles(cfg, thr, reference_order, x_real, require_finite_candidates=False, family=None, cycles=2, **kw):
     """Two control cycles of RobustMPPIController on injected noise, engine and oracle side by side (reference:
     controllers/R-MPPI/robust_mppi_controller.cu:635-755 computeControl, :508-633 updateImportanceSamplingControl;
     core/rmppi_kernels.cu:231-356 initEvalKernel, :666-866 rolloutRMPPIKernel).
@@ -319,7 +319,7 @@ def _robust_two_cycles(cfg, thr, reference_order, x_real, require_finite_candida
     S, C, T, K = eng.STATE_DIM, eng.CONTROL_DIM, cfg["T"], cfg["K"]
     g = np.random.default_rng(5).uniform(-0.3, 0.3, (T, S, C)).astype(np.float32)  # bench.py's gains
     x = cfg["x0"].copy()
-    for cycle in range(2):
+    for cycle in range(cycles):
         eps = host_noise(2, K, T, C, seed=900 + cycle)
         eng.injectNoise(eps[1:] if cycle == 0 else eps)
         eng.updateImportanceSamplingControl(x, 1)
@@ -344,6 +344,8 @@ def _robust_two_cycles(cfg, thr, reference_order, x_real, require_finite_candida
         rob.set_gains(g)
         eng.computeControl(x, 1)
         rob.compute_control(x, 1, eps[1:])
+        if family is not None:  # the kernel that ran, as the launch path recorded it
+            assert eng.getLaunchInfo()["family"] == family, (cycle, eng.getLaunchInfo())
         costs_g, costs_o = eng.getSampledCostSeq(), orc.costs()
         assert costs_g.shape == costs_o.shape == (2, K)
         assert np.isfinite(costs_g).all()
@@ -398,3 +400,47 @@ def test_robust_complete_racer_4096x100_vs_oracle(gpu, variant):
     kv = m.MPPI_KERNEL_PIPELINE if variant == "pipeline" else m.MPPI_KERNEL_FUSED
     _robust_two_cycles(cfg, 2000.0, True, cfg["x0"] + dx, kernel_variant=kv)
     _robust_two_cycles(cfg, 2000.0, False, cfg["x0"] + dx, kernel_variant=kv)
+
+
+def _robust_racer_bench_size(model):
+    """bench.py's `robust_racer_leg` at the size it times it — Robust MPPI on the complete RACER model
+    (RacerDubinsElevationLSTMUncertaintyQuad) and on RacerDubinsElevationSuspensionQuad, K = 16384, T = 100, threshold 2000,
+    9 x 32 candidates, control cost [0.2, 0.1], the bench's gains, the pipelined kernel it times — against the oracle in both
+    reduction modes.  The oracle had stopped at K = 4096 (complete model) and T = 21 (suspension).
+    The reference-order reduction reproduces the oracle bit for bit through both cycles.  The default reduction is held to the
+    oracle where both start from the same inputs (cycle 0: costs 0 ulp, u* <= 1e-5); its second cycle starts from a u* that
+    differs in the seventh digit, and on the suspension model at this size the real system's u* then lands 1.4e-5 away from
+    the oracle's — a difference the reference-order run, which starts both cycles from identical inputs, does not show — so
+    that cycle of the default reduction is compared for the complete model only."""
+    from test_racer_dubins_lstm_unc import uncertainty_cfg
+    from test_racer_dubins_suspension import suspension_cfg
+    cfg = {"complete": uncertainty_cfg, "suspension": suspension_cfg}[model](K=16384, T=100, D=2)
+    cfg["control_cost_coeff"] = [0.2, 0.1]
+    dx = np.zeros_like(cfg["x0"])
+    dx[:7] = [0.3, -0.2, 0.1, 0.05, 0.02, 0.01, 0.0]
+    for reference_order in (True, False):
+        _robust_two_cycles(cfg, 2000.0, reference_order, cfg["x0"] + dx, family="rmppi_pipeline",
+                           cycles=2 if (reference_order or model == "complete") else 1, kernel_variant=m.MPPI_KERNEL_PIPELINE)
+
+
+def test_robust_complete_racer_16384x100_vs_oracle(gpu):
+    _robust_racer_bench_size("complete")
+
+
+def test_robust_suspension_16384x100_vs_oracle(gpu):
+    _robust_racer_bench_size("suspension")
+
+
+@pytest.mark.parametrize("variant", [m.MPPI_KERNEL_PIPELINE, m.MPPI_KERNEL_FUSED], ids=["pipeline", "fused"])
+def test_cartpole_config1_128x100_vs_oracle(gpu, variant):
+    """BASELINE config 1 literally: Cartpole K = 128, T = 100 (examples/cartpole_example.cu parameters), computeControl against
+    the oracle on injected noise, both kernel structures — two blocks, the smallest merge bench.py times"""
+    cfg = cartpole_cfg(K=128, T=100)
+    eng, orc = make_engine(cfg, kernel_variant=variant), make_oracle(cfg)
+    eps = host_noise(1, cfg["K"], cfg["T"], 1, seed=1)
+    eng.injectNoise(eps)
+    eng.computeControl(cfg["x0"], 1)
+    orc.vanilla_compute_control(cfg["x0"], 1, eps)
+    assert eng.getLaunchInfo()["family"] == ("pipeline" if variant == m.MPPI_KERNEL_PIPELINE else "fused")
+    _check_vanilla(eng, orc)
+    eng.close()
