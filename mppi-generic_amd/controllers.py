@@ -20,6 +20,7 @@ MPPI_NOISE_INJECTED = 1
 MPPI_NOISE_ROCRAND_HOST = 2
 MPPI_KERNEL_AUTO, MPPI_KERNEL_FUSED, MPPI_KERNEL_PIPELINE = 0, 1, 2
 MPPI_REDUCTION_FUSED, MPPI_REDUCTION_REFERENCE_ORDER, MPPI_REDUCTION_REFERENCE_ORDER_FMA = 0, 1, 2
+MPPI_ERR_INVALID_ARG = 1
 
 
 class MPPIError(RuntimeError):
@@ -258,7 +259,10 @@ def _f32(a):
 
 
 class MPPIController:
-    """Common part of the reference's Controller<DYN, COST, FB, SAMPLING, MAX_TIMESTEPS, NUM_ROLLOUTS>."""
+    """Common part of the reference's Controller<DYN, COST, FB, SAMPLING, MAX_TIMESTEPS, NUM_ROLLOUTS>.
+
+    A controller object is not thread-safe: computeControl, getControlSeq and slideControlSequence share staging arrays,
+    and the handle underneath holds one control sequence.  Calls on one object come from one thread at a time."""
 
     KIND = MPPI_CONTROLLER_VANILLA
 
@@ -297,7 +301,7 @@ class MPPIController:
         self._fast_get_control = raw("mppi_get_control_seq", C.c_void_p, C.c_void_p)
         self._fast_slide = raw("mppi_slide", C.c_void_p, C.c_int)
         self._hv = self._h.value
-        self._x_stage = np.zeros(2 * self.STATE_DIM, np.float32)  # [S], or [D][S] where a caller hands both systems' states
+        self._x_stage = np.zeros(self.STATE_DIM, np.float32)
         self._x_ptr = self._x_stage.ctypes.data
         self._u_stage = np.empty((self.num_timesteps, self.CONTROL_DIM), np.float32)
         self._u_ptr = self._u_stage.ctypes.data
@@ -440,16 +444,21 @@ class MPPIController:
         return eps
 
     def computeControl(self, state, optimization_stride=1):
+        """state: the measured state, STATE_DIM floats for every controller (mppi_compute_control reads exactly that many:
+        Tube and Robust MPPI keep their nominal state themselves); any other size raises MPPIError(MPPI_ERR_INVALID_ARG)"""
         if type(state) is not np.ndarray:
             state = np.asarray(state, np.float32)
-        n = state.size
-        if n > self._x_stage.size:  # (not a state of this model: let the checked path say so)
-            self._check(self._lib.mppi_compute_control(self._h, _f32(state).reshape(-1), optimization_stride))
-            return
-        self._x_stage[:n] = state if state.ndim == 1 else state.reshape(-1)
+        self._check_state_size(state, "computeControl")
+        self._x_stage[:] = state if state.ndim == 1 else state.reshape(-1)
         st = self._fast_compute(self._hv, self._x_ptr, optimization_stride)
         if st != 0:
             self._check(st)
+
+    def _check_state_size(self, state, what):
+        """the library reads exactly STATE_DIM floats of a measured state: any other size is the caller's error"""
+        if np.size(state) != self.STATE_DIM:
+            raise MPPIError(MPPI_ERR_INVALID_ARG, "%s: a state of %d floats, the model's state has %d"
+                            % (what, np.size(state), self.STATE_DIM))
 
     def getControlSeq(self):
         st = self._fast_get_control(self._hv, self._u_ptr)
@@ -631,6 +640,8 @@ class RobustMPPIController(MPPIController):
         self._check(self._lib.mppi_set_feedback_gains(self._h, g.reshape(-1), int(accumulate_all_states)))
 
     def updateImportanceSamplingControl(self, state, stride):
+        """state: the measured state, STATE_DIM floats; any other size raises MPPIError(MPPI_ERR_INVALID_ARG)"""
+        self._check_state_size(state, "updateImportanceSamplingControl")
         self._check(self._lib.mppi_update_importance_sampling_control(self._h, _f32(state).reshape(-1), stride))
 
     def getRMPPIState(self):

@@ -207,10 +207,11 @@ def _colored_params(C):
     return ([1.0, 0.5][:C], 0.97, 0.0)
 
 
-def _make(case, K, T):
+def _make(case, K, T, num_iters=1):
     D = 2 if case["controller"] in ("tube", "robust") else 1
     cfg = BUILDERS[case["model"]](K, T, D)
     cfg["D"] = D
+    cfg["num_iters"] = num_iters
     if case["controller"] == "colored":
         cfg["colored"] = _colored_params(len(cfg["control_cost_coeff"]))
     old = os.environ.get("MPPI_AMD_ROWS_IN_HBM")
