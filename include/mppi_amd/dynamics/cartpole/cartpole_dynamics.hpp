@@ -102,6 +102,56 @@ public:
         (-force * cos_theta - m_p * l_p * SQ(theta_dot) * cos_theta * sin_theta - (m_c + m_p) * gravity_ * sin_theta);
   }
 
+  /* Split step (plugin/dynamics.hpp): only (theta, theta_dot) feed back — the cart's x and x_dot integrate values the angle
+   * chain produces.  The core advances the angle pair; the completion, on the pipelined kernel's cost wave, rebuilds the cart
+   * from sin, cos and the new theta_dot.  Both halves repeat computeDynamics' expressions and updateState's Euler step
+   * operation for operation (fp contraction is off), so next state and output are step()'s bits. */
+  using SPLIT_STEP_CLASS = CartpoleDynamics;
+  static constexpr int SPLIT_CARRY = 3;  // theta_dot_{t+1}, sin(theta_t), cos(theta_t)
+
+  __device__ inline void stepCore(const float* state, float* next_state, const float* control, float* carry, const float dt)
+  {
+    float theta_n = angle_utils::normalizeAngleBounded(state[2]);
+    float sin_theta, cos_theta;
+    mppi::det::sincos(theta_n, &sin_theta, &cos_theta);
+    float theta_dot = state[3];
+    float force = control[0];
+    float m_c = this->params_.cart_mass;
+    float m_p = this->params_.pole_mass;
+    float l_p = this->params_.pole_length;
+    const float den = m_c + m_p * SQ(sin_theta);
+    // rcp_benign2's second lane alone: the same correctly rounded reciprocal; the first (the cart's) is the completion's
+    const float r_th = mppi::det::rcp_benign(l_p * den);
+    const float theta_dd =
+        r_th *
+        (-force * cos_theta - m_p * l_p * SQ(theta_dot) * cos_theta * sin_theta - (m_c + m_p) * gravity_ * sin_theta);
+    next_state[2] = state[2] + theta_dot * dt;
+    next_state[3] = theta_dot + theta_dd * dt;
+    carry[0] = next_state[3];
+    carry[1] = sin_theta;
+    carry[2] = cos_theta;
+  }
+
+  __device__ inline void stepComplete(float* state, const float* control, const float* carry, float* output, const float dt)
+  {
+    const float sin_theta = carry[1], cos_theta = carry[2];
+    float theta_dot = state[3];
+    float force = control[0];
+    float m_c = this->params_.cart_mass;
+    float m_p = this->params_.pole_mass;
+    float l_p = this->params_.pole_length;
+    const float den = m_c + m_p * SQ(sin_theta);
+    const float r_x = mppi::det::rcp_benign(den);
+    const float x_dd = r_x * (force + m_p * sin_theta * (l_p * SQ(theta_dot) + gravity_ * cos_theta));
+    state[0] = state[0] + state[1] * dt;
+    state[1] = state[1] + x_dd * dt;
+    state[2] = state[2] + theta_dot * dt;
+    state[3] = carry[0];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      output[i] = state[i];
+  }
+
 protected:
   const float gravity_ = 9.81;
 };

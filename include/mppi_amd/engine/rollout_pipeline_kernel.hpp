@@ -36,6 +36,7 @@
 #include "rollout_kernel.hpp"
 #include "merge_wave.hpp"
 #include "kernarg_view.hpp"
+#include "mppi_amd/plugin/dynamics.hpp"  // split_step
 
 namespace mppi
 {
@@ -47,6 +48,17 @@ constexpr int PIPE_ROLES = 3;
 __host__ __device__ constexpr int pipeRingSteps(int output_dim)
 {
   return output_dim <= 8 ? 32 : (output_dim <= 16 ? 16 : 8);
+}
+
+/** floats per step and rollout the dynamics wave hands the cost wave through the ring: the output y_t, or — for a plugin that
+ *  declares the split step (plugin/dynamics.hpp) — the carry of its core, from which the cost wave completes the step */
+template <class DYN_T>
+__host__ __device__ constexpr int pipeRingOutputFloats()
+{
+  if constexpr (split_step<DYN_T>::value)
+    return DYN_T::SPLIT_CARRY;
+  else
+    return DYN_T::OUTPUT_DIM;
 }
 
 /** fold_z: the systems of a rollout are folded into the LANE dimension (64 / bz rollouts x bz systems per wave) instead of
@@ -64,7 +76,7 @@ __host__ inline size_t pipelineSharedBytes(const DYN_T& dyn, const COST_T& cost,
   n += sizeof(float) * 2 * math::nearest_multiple_4(slots);                     // cost_s, w_s
   // output ring [z][slot][i][lane]; with the rows in HBM the clamped control travels through it as well
   n += sizeof(float) * (size_t)rings * pipeRingSteps(DYN_T::OUTPUT_DIM) *
-       (DYN_T::OUTPUT_DIM + (smp.rows_global_d_ ? DYN_T::CONTROL_DIM : 0)) * 64;
+       (pipeRingOutputFloats<DYN_T>() + (smp.rows_global_d_ ? DYN_T::CONTROL_DIM : 0)) * 64;
   n += sizeof(int) * 4 * 4 * rings;                                              // progress counters (padded)
   // STREAM_MERGE: the control mean the sampler waves merge for themselves, [T][C], for the cost wave's likelihood-ratio term
   n += sizeof(float) * math::nearest_multiple_4(smp.params_.num_timesteps * DYN_T::CONTROL_DIM);
@@ -243,7 +255,11 @@ __global__ void __launch_bounds__(pipelineBlockX(BZ, FOLD_Z) * (FOLD_Z ? 1 : BZ)
     theta_d_shared = sampling->blockRows(theta_d_lds, (int)blockIdx.x, SLOTS);
     sampling->setStagingBase(theta_d_lds);
   }
-  constexpr int F = O + (ROWS_HBM ? C : 0);  // floats per step and rollout in the output ring
+  // Split step: the dynamics wave runs the plugin's core (the recurrent states) and rings its carry; the cost wave keeps its
+  // own copy of the state and completes the step in front of the running cost
+  constexpr bool SPLIT = split_step<DYN_T>::value;
+  constexpr int RY = pipeRingOutputFloats<DYN_T>();
+  constexpr int F = RY + (ROWS_HBM ? C : 0);  // floats per step and rollout in the output ring
   float* cost_s = theta_d_lds + calcClassSharedMemSize(sampling, SLOTS) / (int)sizeof(float);
   float* w_s = cost_s + math::nearest_multiple_4(SLOTS);
   float* ring_all = w_s + math::nearest_multiple_4(SLOTS);
@@ -525,16 +541,27 @@ __global__ void __launch_bounds__(pipelineBlockX(BZ, FOLD_Z) * (FOLD_Z ? 1 : BZ)
         for (int i = 0; i < C; i++)
           row[t * C + i] = u[i];
       }
-      dynamics->step(xc, xn, xdot, u, y, theta_s_shared, t, dt);
       float* slot = ring + (size_t)(t % PIPE_RING) * F * 64 + lane;
+      if constexpr (SPLIT)
+      {
+        float carry[RY];
+        dynamics->stepCore(xc, xn, u, carry, dt);
 #pragma unroll
-      for (int i = 0; i < O; i++)
-        slot[i * 64] = y[i];
+        for (int i = 0; i < RY; i++)
+          slot[i * 64] = carry[i];
+      }
+      else
+      {
+        dynamics->step(xc, xn, xdot, u, y, theta_s_shared, t, dt);
+#pragma unroll
+        for (int i = 0; i < O; i++)
+          slot[i * 64] = y[i];
+      }
       if constexpr (ROWS_HBM)
       {
 #pragma unroll
         for (int i = 0; i < C; i++)
-          slot[(O + i) * 64] = u[i];
+          slot[(RY + i) * 64] = u[i];
       }
     };
     int seen_smp = 0, seen_smp1 = 0, seen_cost = 0;
@@ -660,11 +687,22 @@ __global__ void __launch_bounds__(pipelineBlockX(BZ, FOLD_Z) * (FOLD_Z ? 1 : BZ)
     auto cost_step = [&](const int tt) {
       const float* slot = ring + (size_t)(tt % PIPE_RING) * F * 64 + lane;
 #pragma unroll
-      for (int i = 0; i < O; i++)
-        y[i] = slot[i * 64];
-#pragma unroll
       for (int i = 0; i < C; i++)
-        u[i] = ROWS_HBM ? slot[(O + i) * 64] : row[tt * C + i];
+        u[i] = ROWS_HBM ? slot[(RY + i) * 64] : row[tt * C + i];
+      if constexpr (SPLIT)
+      {  // x: this wave's copy of the state (the initial state, then what the completions made of it)
+        float carry[RY];
+#pragma unroll
+        for (int i = 0; i < RY; i++)
+          carry[i] = slot[i * 64];
+        dynamics->stepComplete(x, u, carry, y, dt);
+      }
+      else
+      {
+#pragma unroll
+        for (int i = 0; i < O; i++)
+          y[i] = slot[i * 64];
+      }
       running_cost += costs->computeRunningCost(y, u, tt, theta_c_shared, &crash_status) +
                       sampling->template computeLikelihoodRatioCost<FOLD_Z, STREAM_MERGE>(u, theta_d_shared, global_idx, tt,
                                                                                           distribution_idx, args.lambda,

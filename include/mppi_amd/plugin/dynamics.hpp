@@ -297,4 +297,32 @@ public:
 };
 }  // namespace MPPI_internal
 
+namespace mppi
+{
+/**
+ * Split step (opt-in, one lane per rollout): step() cut in two for the role-pipelined rollout kernel
+ * (engine/rollout_pipeline_kernel.hpp), whose dynamics wave carries the step-to-step recurrence and whose cost wave has
+ * issue slots to spare.  A plugin declares
+ *
+ *   using SPLIT_STEP_CLASS = <the class itself>;
+ *   static constexpr int SPLIT_CARRY = <floats handed from the core to the completion>;
+ *   __device__ void stepCore(const float* state, float* next_state, const float* control, float* carry, float dt);
+ *       advances the states the recurrence needs (writes only those of next_state) and fills carry[SPLIT_CARRY]
+ *   __device__ void stepComplete(float* state, const float* control, const float* carry, float* output, float dt);
+ *       on another wave, with its own copy of the state: replaces `state` by the next state and writes the output
+ *
+ * The pair must compute next state and output with exactly the fp32 operations of step() (state_der and theta_s are not
+ * produced), so the kernel may take either path.  The declaration binds to the most-derived class only: a class derived
+ * from a split plugin (which may change the dynamics) does not repeat it and runs step().
+ */
+template <class T, class = void>
+struct split_step : std::false_type
+{
+};
+template <class T>
+struct split_step<T, std::void_t<typename T::SPLIT_STEP_CLASS>> : std::is_same<typename T::SPLIT_STEP_CLASS, T>
+{
+};
+}  // namespace mppi
+
 #endif

@@ -4,8 +4,10 @@
 Usage: isa_step_count.py [out.json]
 For every entry of KERNELS: compile the model's translation unit device-only (tools/isa_tu.py's cache), take the kernel
 whose mangled name contains all the given substrings, list its loops (backward branches) and pick the INNERMOST loop with
-the most packed-fp32 / MFMA instructions — the dynamics wave's step loop (sampler and cost waves use neither) — and divide
-its instruction counts by the steps one trip of that loop covers.  bench.py multiplies `instructions_per_step` with the
+the most packed-fp32 / MFMA instructions — the dynamics wave's step loop — and divide its instruction counts by the steps one
+trip of that loop covers.  Where another wave's loop holds packed arithmetic too (the Cartpole cost wave completes the split
+step, round 7), an entry also names an opcode the loop must contain and one it must not: the dynamics wave STORES the output
+ring ([slot][i][lane]: ds_write2st64_b32), the cost wave READS it.  bench.py multiplies `instructions_per_step` with the
 issue interval it measures live (mppi_measure_issue_interval) to get a floor that does not depend on the timing of the
 kernel being judged (roofline.issue_floor); tests/test_abi.py checks that the committed file is what the current sources
 compile to."""
@@ -18,12 +20,16 @@ from collections import Counter
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_tu  # noqa: E402
 
-# (key, translation unit, kernel-name substrings, steps per trip of the dynamics loop, marker class)
+# (key, translation unit, kernel-name substrings, steps per trip of the loop, marker class[, (opcode the loop contains,
+#  opcode it does not)])
+CARTPOLE_HEADLINE = ["rolloutPipelineKernel", "Cartpole", "GaussianDistribution", "ELi1ELb1ELb0ELb0ELb1EE"]
 KERNELS = [
     # (template tails: <.., BZ = 1, DRAW_IN_LOOP, FOLD_Z = false, ROWS_HBM = false, STREAM_MERGE = true> — the instantiation the
     #  iterations of the headline run — / <.., DRAW_IN_LOOP, ROWS_HBM = false>)
-    ("cartpole_pipeline_dynamics_wave", "cartpole.hip",
-     ["rolloutPipelineKernel", "Cartpole", "GaussianDistribution", "ELi1ELb1ELb0ELb0ELb1EE"], 8, "valu_pk"),  # round 4: eight steps per trip
+    ("cartpole_pipeline_dynamics_wave", "cartpole.hip", CARTPOLE_HEADLINE, 8, "valu_pk",
+     ("ds_write2st64_b32", None)),  # round 4: eight steps per trip
+    ("cartpole_pipeline_cost_wave", "cartpole.hip", CARTPOLE_HEADLINE, 4, "valu_pk",
+     ("ds_read2st64_b32", "ds_write2st64_b32")),  # four steps per trip
     ("autorally_mfma_pipeline_dynamics_wave", "autorally_nn.hip",
      ["rolloutPipelineRepKernel", "NeuralNetModelMFMA", "GaussianDistribution", "ELb1ELb0EE"], None, "mfma"),
     ("lstm_mfma_pipeline_dynamics_wave", "bicycle_slip_lstm.hip",
@@ -65,7 +71,8 @@ def main():
     units = sorted({os.path.join(isa_tu.REPO, "mppi-generic_amd", "csrc", "models", k[1]) for k in KERNELS})
     with concurrent.futures.ThreadPoolExecutor(max_workers=len(units)) as pool:
         list(pool.map(isa_tu.disassemble, units))
-    for key, tu, subs, steps, marker in KERNELS:
+    for key, tu, subs, steps, marker, *pick in KERNELS:
+        has, has_not = pick[0] if pick else (None, None)
         cands = loops_of(tu, subs)
         if not cands:
             res[key] = {"error": "kernel not found"}
@@ -73,6 +80,8 @@ def main():
         name, loops = cands[0]
         best = None
         for ops in loops:
+            if (has and has not in ops) or (has_not and has_not in ops):
+                continue
             c = Counter(isa_tu.classify(o) for o in ops)
             score = (c.get(marker, 0), -len(ops))
             if c.get(marker, 0) and (best is None or score > best[0]):
