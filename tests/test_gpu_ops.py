@@ -7,7 +7,7 @@ import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import cartpole_cfg, host_noise, make_engine, make_oracle, merge_records_numpy, ulp_diff
+from common import cartpole_cfg, host_noise, make_engine, make_oracle, ulp_diff
 
 pytestmark = pytest.mark.gpu
 
