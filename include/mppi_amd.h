@@ -33,7 +33,7 @@ extern "C" {
 #endif
 
 #define MPPI_AMD_VERSION_MAJOR 0
-#define MPPI_AMD_VERSION_MINOR 1
+#define MPPI_AMD_VERSION_MINOR 2
 
 typedef struct mppi_handle_s* mppi_handle;
 
@@ -178,7 +178,9 @@ const char* mppi_source_hash(void);
 typedef enum mppi_sampler_kind
 {
   MPPI_SAMPLER_GAUSSIAN = 0, /* used by the Vanilla / Tube / Robust controllers */
-  MPPI_SAMPLER_COLORED = 1   /* used by MPPI_CONTROLLER_COLORED */
+  MPPI_SAMPLER_COLORED = 1,  /* used by MPPI_CONTROLLER_COLORED */
+  MPPI_SAMPLER_NLN = 2       /* normal-log-normal noise (log-MPPI; sampling_distributions/nln/nln.cuh), for the Vanilla / Tube /
+                              * Robust controllers through mppi_create_with_sampler */
 } mppi_sampler_kind;
 /** returns a new mppi::engine::ModelBase* (owned by the handle that asked for it) */
 typedef void* (*mppi_model_factory)(void);
@@ -217,6 +219,18 @@ mppi_status mppi_describe_model(const char* name, int sampler_kind, int* shapes,
 /* ---------------------------------------------------------------- lifecycle -------------------------------------- */
 /** Controller constructor + GPUSetup + allocateCUDAMemory (controllers/controller.cuh:160-216, 269-277, 931-992) */
 mppi_status mppi_create(const mppi_config* cfg, mppi_handle* out);
+/**
+ * mppi_create with the sampling distribution named (the reference's SAMPLING_T template argument): the Vanilla, Tube and Robust
+ * controllers take MPPI_SAMPLER_GAUSSIAN or MPPI_SAMPLER_NLN, MPPI_CONTROLLER_COLORED takes MPPI_SAMPLER_COLORED only; any
+ * other combination is MPPI_ERR_INVALID_ARG, a (model, sampler) pair that is not registered MPPI_ERR_UNKNOWN_MODEL.
+ * mppi_create(cfg, out) is mppi_create_with_sampler(cfg, COLORED for MPPI_CONTROLLER_COLORED else GAUSSIAN, out).
+ * NLN: eps' = z * exp(std_dev[c] * z') with z, z' from Philox streams s and 16 + s (mppi_amd/sampling_distributions/nln.hpp);
+ * injected noise is taken as eps' itself; MPPI_NOISE_ROCRAND_HOST is refused with MPPI_ERR_UNSUPPORTED (the host generator
+ * fills one normal tensor, the NLN draw needs two and their product).
+ */
+mppi_status mppi_create_with_sampler(const mppi_config* cfg, int sampler_kind, mppi_handle* out);
+/** the mppi_sampler_kind a handle was created with; -1 for a null handle */
+int mppi_get_sampler_kind(mppi_handle h);
 /** Controller destructor + freeCudaMem (controllers/controller.cuh:194-216) */
 void mppi_destroy(mppi_handle h);
 /** message of the last failing call; h == NULL: last mppi_create failure of this thread */

@@ -44,7 +44,7 @@ class Controller
 public:
   Controller(const std::string& model, int controller_kind, int num_rollouts, int num_timesteps, float dt, int max_iter,
              float lambda, float alpha, unsigned long long seed = 42, int device = 0, int rank = 0, int world_size = 1,
-             void* stream = nullptr)
+             void* stream = nullptr, int sampler_kind = -1)
     : num_rollouts_(num_rollouts), num_timesteps_(num_timesteps), dt_(dt)
   {
     mppi_config cfg{};
@@ -62,7 +62,8 @@ public:
     cfg.stream = stream;
     cfg.rank = rank;
     cfg.world_size = world_size;
-    const mppi_status s = mppi_create(&cfg, &h_);
+    // sampler_kind < 0: the controller kind's own sampler (Gaussian; colored noise for MPPI_CONTROLLER_COLORED)
+    const mppi_status s = sampler_kind < 0 ? mppi_create(&cfg, &h_) : mppi_create_with_sampler(&cfg, sampler_kind, &h_);
     if (s != MPPI_OK)
       throw Error(s, std::string("mppi_create: ") + mppi_last_error(nullptr));
     check(mppi_get_dims(h_, &state_dim_, &control_dim_, &output_dim_, &num_systems_));
@@ -138,6 +139,11 @@ public:
   void getLaunchCounts(unsigned long long& rollout_launches, unsigned long long& merge_launches) const
   {
     check(mppi_get_launch_counts(h_, &rollout_launches, &merge_launches));
+  }
+  /** the mppi_sampler_kind the handle was created with (MPPI_SAMPLER_GAUSSIAN, _COLORED, _NLN) */
+  int getSamplerKind() const
+  {
+    return mppi_get_sampler_kind(h_);
   }
   void setSeed(unsigned long long seed)
   {
@@ -328,8 +334,9 @@ class VanillaMPPIController : public Controller
 {
 public:
   VanillaMPPIController(const std::string& model, int num_rollouts, int num_timesteps, float dt, int max_iter, float lambda,
-                        float alpha, unsigned long long seed = 42, int device = 0)
-    : Controller(model, MPPI_CONTROLLER_VANILLA, num_rollouts, num_timesteps, dt, max_iter, lambda, alpha, seed, device)
+                        float alpha, unsigned long long seed = 42, int device = 0, int sampler_kind = MPPI_SAMPLER_GAUSSIAN)
+    : Controller(model, MPPI_CONTROLLER_VANILLA, num_rollouts, num_timesteps, dt, max_iter, lambda, alpha, seed, device, 0, 1, nullptr,
+                 sampler_kind)
   {
   }
 };
@@ -339,8 +346,9 @@ class TubeMPPIController : public Controller
 {
 public:
   TubeMPPIController(const std::string& model, int num_rollouts, int num_timesteps, float dt, int max_iter, float lambda,
-                     float alpha, unsigned long long seed = 42, int device = 0)
-    : Controller(model, MPPI_CONTROLLER_TUBE, num_rollouts, num_timesteps, dt, max_iter, lambda, alpha, seed, device)
+                     float alpha, unsigned long long seed = 42, int device = 0, int sampler_kind = MPPI_SAMPLER_GAUSSIAN)
+    : Controller(model, MPPI_CONTROLLER_TUBE, num_rollouts, num_timesteps, dt, max_iter, lambda, alpha, seed, device, 0, 1, nullptr,
+                 sampler_kind)
   {
   }
   void setNominalThreshold(float t)
@@ -382,8 +390,10 @@ class RobustMPPIController : public Controller
 public:
   RobustMPPIController(const std::string& model, int num_rollouts, int num_timesteps, float dt, int max_iter, float lambda,
                        float alpha, float value_function_threshold, int num_candidate_nominal_states = 9,
-                       int samples_per_candidate = 32, unsigned long long seed = 42, int device = 0)
-    : Controller(model, MPPI_CONTROLLER_ROBUST, num_rollouts, num_timesteps, dt, max_iter, lambda, alpha, seed, device)
+                       int samples_per_candidate = 32, unsigned long long seed = 42, int device = 0,
+                       int sampler_kind = MPPI_SAMPLER_GAUSSIAN)
+    : Controller(model, MPPI_CONTROLLER_ROBUST, num_rollouts, num_timesteps, dt, max_iter, lambda, alpha, seed, device, 0, 1, nullptr,
+                 sampler_kind)
   {
     check(mppi_set_rmppi_params(h_, value_function_threshold, num_candidate_nominal_states, samples_per_candidate));
     num_candidates_ = num_candidate_nominal_states;

@@ -101,7 +101,7 @@ inline const std::string& registeredModelName()
     // not share a registration: the parameter layouts differ)
     std::string n = std::string("tpl:") + typeid(DYN_T).name() + ":" + typeid(COST_T).name() + ":" + typeid(SAMPLING_T).name();
     const mppi_status s =
-        mppi_register_model_checked(n.c_str(), SAMPLING_T::COLORED ? MPPI_SAMPLER_COLORED : MPPI_SAMPLER_GAUSSIAN,
+        mppi_register_model_checked(n.c_str(), SAMPLING_T::SAMPLER_KIND,
                                     &modelFactory<MODEL, 64, 1>, engineAbiFingerprint(), modelFlags<MODEL>());
     if (s != MPPI_OK)
       throw Error(s, "mppi_register_model failed for " + n + ": " + mppi_last_error(nullptr));
@@ -346,7 +346,8 @@ protected:
     // for the engine's default, anything else has to be one of RolloutShapes<...>::type (the reference's (64, 4, 1) is)
     cfg.block_x = (int)params_.dynamics_rollout_dim_.x;
     cfg.block_y = (int)params_.dynamics_rollout_dim_.y;
-    const mppi_status s = mppi_create(&cfg, &h_);
+    // the sampler class names the registration's sampler kind (GaussianDistribution, ColoredNoiseDistribution, NLNDistribution)
+    const mppi_status s = mppi_create_with_sampler(&cfg, SAMPLING_T::SAMPLER_KIND, &h_);
     if (s == MPPI_ERR_LAUNCH_SHAPE)
       throw Error(s, std::string("mppi_create: ") + mppi_last_error(nullptr) +
                          " — dynamics_rollout_dim_ has to be (0, 0, .) or one of mppi_amd::templated::RolloutShapes<DYN_T, COST_T, "

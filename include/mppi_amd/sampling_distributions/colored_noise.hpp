@@ -299,6 +299,7 @@ public:
   static const int CONTROL_DIM = PARENT::CONTROL_DIM;
   static constexpr bool IN_LOOP_DRAW = false;  ///< the rows are filled by the prologue GEMM
   static constexpr bool COLORED = true;
+  static constexpr int SAMPLER_KIND = 1;  ///< MPPI_SAMPLER_COLORED
   /** long horizons: the prologue GEMM writes its tiles straight into the HBM rows (the accumulators are registers; only the
    *  table staging tiles need the LDS), the step loop reads them back through sampleRow() like the Gaussian sampler */
   static constexpr bool SUPPORTS_GLOBAL_ROWS = true;

@@ -83,6 +83,7 @@ public:
   typedef GaussianDistribution<DYN_PARAMS_T> SAMPLING_T;
   static constexpr bool IN_LOOP_DRAW = true;  ///< single-lane rollouts may draw eps inside the step loop
   static constexpr bool COLORED = false;
+  static constexpr int SAMPLER_KIND = 0;  ///< mppi_sampler_kind (mppi_amd.h) a model with this sampler registers under
   /** the fused rollout kernel can keep this sampler's rows in global memory when they do not fit the LDS (long horizons) */
   static constexpr bool SUPPORTS_GLOBAL_ROWS = true;
 

@@ -81,6 +81,8 @@ SIGNATURES = {
     "mppi_describe_model": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
                                       C.POINTER(C.c_uint)]),
     "mppi_create": (C.c_int, [C.POINTER(MppiConfig), C.POINTER(H)]),
+    "mppi_create_with_sampler": (C.c_int, [C.POINTER(MppiConfig), C.c_int, C.POINTER(H)]),
+    "mppi_get_sampler_kind": (C.c_int, [H]),
     "mppi_destroy": (None, [H]),
     "mppi_last_error": (C.c_char_p, [H]),
     "mppi_get_dims": (C.c_int, [H] + [C.POINTER(C.c_int)] * 4),

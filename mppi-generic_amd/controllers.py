@@ -268,14 +268,19 @@ class MPPIController:
 
     def __init__(self, model, num_rollouts, num_timesteps, dt, lambda_, alpha=0.0, num_iters=1, seed=42,
                  noise_source=MPPI_NOISE_PHILOX_FUSED, block_x=0, block_y=0, device=0, stream=None, rank=0,
-                 world_size=1, save_samples=False, kernel_variant=0, force_exchange=False):
+                 world_size=1, save_samples=False, kernel_variant=0, force_exchange=False, sampler=None):
+        """sampler: an MPPI_SAMPLER_* constant, the reference's SAMPLING_T.  None is the controller's own (Gaussian; colored noise
+        for ColoredMPPIController); the Vanilla, Tube and Robust controllers also take MPPI_SAMPLER_NLN (log-MPPI)."""
         self._lib = load_library()
         self._h = C.c_void_p()
         self._model = model.encode()
         cfg = MppiConfig(self._model, self.KIND, num_rollouts, num_timesteps, dt, lambda_, alpha, num_iters, seed,
                          noise_source, block_x, block_y, device, stream, rank, world_size, int(save_samples), kernel_variant,
                          int(force_exchange))
-        st = self._lib.mppi_create(C.byref(cfg), C.byref(self._h))
+        if sampler is None:
+            st = self._lib.mppi_create(C.byref(cfg), C.byref(self._h))
+        else:
+            st = self._lib.mppi_create_with_sampler(C.byref(cfg), int(sampler), C.byref(self._h))
         if st != 0:
             self._h = C.c_void_p()
             raise MPPIError(st, (self._lib.mppi_last_error(None) or b"").decode())
@@ -287,6 +292,7 @@ class MPPIController:
         self.num_rollouts_local, self.rollout_offset = kl.value, ko.value
         self.num_rollouts, self.num_timesteps = num_rollouts, num_timesteps
         self.dt, self.lambda_, self.alpha = dt, lambda_, alpha
+        self.sampler = self._lib.mppi_get_sampler_kind(self._h)
         self._init_fast_calls()
 
     def _init_fast_calls(self):
@@ -686,6 +692,7 @@ class TubeMPPIController(MPPIController):
 KERNEL_FAMILIES = ("none", "fused", "fused_rep", "pipeline", "pipeline_fold", "pipeline_rep", "rmppi", "rmppi_pipeline")
 MPPI_SAMPLER_GAUSSIAN = 0
 MPPI_SAMPLER_COLORED = 1
+MPPI_SAMPLER_NLN = 2
 _MODEL_CAPS = (("pipeline", 1), ("rmppi", 2), ("rmppi_pipeline", 4), ("rows_in_hbm", 8), ("streamed_merge", 16),
                ("pipeline_fold", 32))
 

@@ -65,13 +65,13 @@ inline ModelRegistry& registry()
   static ModelRegistry* r = new ModelRegistry();  // never destroyed: plugins may unregister nothing at exit
   return *r;
 }
-inline ModelBase* makeModel(const std::string& name, bool colored)
+inline ModelBase* makeModel(const std::string& name, int sampler_kind)
 {
   ModelRegistry& r = registry();
   mppi_model_factory f = nullptr;
   {
     std::lock_guard<std::mutex> lock(r.mu);
-    auto it = r.factories.find({ name, colored ? MPPI_SAMPLER_COLORED : MPPI_SAMPLER_GAUSSIAN });
+    auto it = r.factories.find({ name, sampler_kind });
     if (it != r.factories.end())
       f = it->second;
   }
@@ -212,6 +212,7 @@ struct mppi_handle_s
   bool independent_noise = false;  // use_same_noise_for_all_distributions == false (sampling_distribution.cuh:20)
   int external_iteration = 0;  // opt_iter of a caller-driven loop (mppi_iteration_local), reset by mppi_upload_state
   int noise_source = MPPI_NOISE_PHILOX_FUSED;
+  int sampler_kind = MPPI_SAMPLER_GAUSSIAN;  // mppi_sampler_kind of the model instantiation (mppi_create_with_sampler)
 
   /* Robust MPPI (controllers/R-MPPI/robust_mppi_controller.cuh:46-53, 270-310) */
   float value_function_threshold = 1000.0f;

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Times optimisation iterations of the registered workloads for several block shapes (HIP events on the engine's
-stream).  Usage: python tools/time_workloads.py [cartpole|autorally|di|lstm|racer] ..."""
+stream).  Usage: python tools/time_workloads.py [cartpole|autorally|di|lstm|racer|nln|nln-gaussian] ...
+(nln / nln-gaussian: the Cartpole pipeline kernel at K = 16384, T = 100 with the NLN and with the Gaussian sampler, one workload
+each so that a kernel trace of either holds one rollout kernel; not part of the default set)"""
 import os
 import sys
 
@@ -11,12 +13,12 @@ import numpy as np  # noqa: E402
 from common import autorally_cfg, bicycle_lstm_cfg, cartpole_cfg, di_cfg, make_engine  # noqa: E402
 
 
-def run(name, cfg, shapes, n=100):
+def run(name, cfg, shapes, n=100, **kw):
     for sh in shapes:
         bx, by = sh[0], sh[1]
         variant = sh[2] if len(sh) > 2 else 0
         try:
-            eng = make_engine(cfg, block_x=bx, block_y=by, kernel_variant=variant)
+            eng = make_engine(cfg, block_x=bx, block_y=by, kernel_variant=variant, **kw)
         except Exception as e:  # noqa: BLE001
             print(name, (bx, by), "skip:", e)
             continue
@@ -33,6 +35,14 @@ which = sys.argv[1:] or ["cartpole", "autorally", "di", "lstm", "racer"]
 if "cartpole" in which:
     run("cartpole", cartpole_cfg(K=16384, T=100), [(64, 1, 1), (64, 1, 2), (32, 1)])
     run("cartpole", cartpole_cfg(K=2048, T=100), [(64, 1)])
+if "nln" in which or "nln-gaussian" in which:
+    import mppi_generic_amd as m  # noqa: E402
+    nln_cfg = cartpole_cfg(K=16384, T=100)
+    nln_cfg["std_dev"] = [0.8]  # exp(std_dev z') as the log-normal factor: 5.0 would pin every sample at the control range
+    if "nln-gaussian" in which:
+        run("cartpole", nln_cfg, [(64, 1, 2)], n=300)
+    if "nln" in which:
+        run("cartpole+nln", nln_cfg, [(64, 1, 2)], n=300, sampler=m.MPPI_SAMPLER_NLN)
 if "autorally" in which:
     # (0, 0, v): the model's default shape — (64, 4), or (64, 8) in the eight-lanes-per-rollout A/B build
     run("autorally", autorally_cfg(K=16384, T=150, lambda_=1.0), [(0, 0, 1), (0, 0, 2), (32, 4), (32, 8)], n=30)
