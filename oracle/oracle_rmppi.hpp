@@ -347,7 +347,7 @@ struct RobustController
                          c->slide_scale.data());
     computeStateTrajectory(*c->dyn, c->dt, nominal_state.data(), c->nominal_control.data(), T, c->nominal_state.data());
   }
-  /** reference: robust_mppi_controller.cu:635-755.  eps: [num_iters][K][T][C] */
+  /** reference: robust_mppi_controller.cu:635-755.  eps: [num_iters][K][T][C], [num_iters][2][K][T][C] with independent noise */
   void computeControl(const float* state, int stride, const float* eps)
   {
     const int S = c->dyn->S, C = c->dyn->C, T = c->T, K = c->K;
@@ -361,7 +361,9 @@ struct RobustController
     {
       std::copy(c->nominal_control.begin(), c->nominal_control.end(), mean.begin());
       std::copy(c->nominal_control.begin(), c->nominal_control.end(), mean.begin() + (size_t)T * C);
-      c->smp.setGaussianControls(mean.data(), eps + (size_t)it * K * T * C, stride, it, c->v.data());
+      /* one block of noise per iteration, or one per iteration and distribution (use_same_noise_for_all_distributions off) */
+      c->smp.setGaussianControls(mean.data(), eps + (size_t)it * K * T * C * (c->smp.independent_noise ? 2 : 1), stride, it,
+                                 c->v.data());
       rmppiRolloutCosts(*c->dyn, *c->cost, c->smp, fb, c->dt, c->lambda, c->alpha, value_function_threshold, x0.data(),
                         mean.data(), c->v.data(), c->costs.data());
       c->w = c->costs;

@@ -207,7 +207,9 @@ def _colored_params(C):
     return ([1.0, 0.5][:C], 0.97, 0.0)
 
 
-def _make(case, K, T, num_iters=1):
+def _make(case, K, T, num_iters=1, overlay=None):
+    """overlay: cfg entries that replace the builder's (and the Robust coefficients below) — the sampler options of
+    tests/test_sampler_options_matrix.py; None leaves the configuration every test here runs on"""
     D = 2 if case["controller"] in ("tube", "robust") else 1
     cfg = BUILDERS[case["model"]](K, T, D)
     cfg["D"] = D
@@ -220,10 +222,12 @@ def _make(case, K, T, num_iters=1):
         if case["controller"] == "robust":
             from test_rmppi import _make_pair
             cfg["control_cost_coeff"] = [0.2, 0.1][:len(cfg["control_cost_coeff"])]
+            cfg.update(overlay or {})
             # 9 x 32 candidate rollouts as bench.py; fewer rollouts than that take the smallest candidate set (3, odd) that fits
             nc, ns = (9, 32) if K >= 9 * 32 else (3, K // 3)
             eng, orc, rob = _make_pair(cfg, nc=nc, ns=ns, save_samples=True, **case["kw"])
         else:
+            cfg.update(overlay or {})
             eng, orc, rob = make_engine(cfg, tube=D == 2, save_samples=True, **case["kw"]), make_oracle(cfg), None
     finally:
         if old is None:

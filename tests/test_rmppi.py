@@ -55,7 +55,7 @@ def _make_pair(cfg, thr=1000.0, nc=9, ns=32, **kw):
         eng.setModelBlob(name, blob)
     if cfg["ranges"] is not None:
         eng.setControlRanges(cfg["ranges"])
-    eng.setSamplingParams(cfg["std_dev"], cfg["control_cost_coeff"])
+    eng.setSamplingParams(cfg["std_dev"], cfg["control_cost_coeff"], cfg.get("pure_pct", 0.01), cfg.get("decay", 1.0))
     eng.setRMPPIParams(thr, nc, ns)
     orc = make_oracle(cfg)
     rob = po.RobustOracle(orc, thr, nc, ns)
