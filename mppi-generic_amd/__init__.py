@@ -6,7 +6,9 @@ classes (same method names) on top of those entry points so tests read like the 
 """
 from . import buildlib as _buildlib
 from .buildlib import build
-from .capi import (MppiTexture2dParams, MppiConfig, MppiGaussianParams, MppiStats, MppiSystemStats, SIGNATURES, library_path, load_library)
+from .capi import (MPPI_OK, MPPI_ERR_INVALID_ARG, MPPI_ERR_UNKNOWN_MODEL, MPPI_ERR_NO_DEVICE, MPPI_ERR_HIP, MPPI_ERR_LAUNCH_SHAPE,
+                   MPPI_ERR_LDS_OVERFLOW, MPPI_ERR_STATE, MPPI_ERR_NAN, MPPI_ERR_COMM, MPPI_ERR_UNSUPPORTED,
+                   MppiTexture2dParams, MppiConfig, MppiGaussianParams, MppiStats, MppiSystemStats, SIGNATURES, library_path, load_library)
 from .controllers import (MPPI_KERNEL_AUTO, MPPI_KERNEL_FUSED, MPPI_KERNEL_PIPELINE, MPPI_CONTROLLER_TUBE, MPPI_CONTROLLER_VANILLA, MPPI_NOISE_INJECTED, MPPI_NOISE_PHILOX_FUSED,
                           MPPIError, MPPIController, TubeMPPIController, VanillaMPPIController, ColoredMPPIController, RobustMPPIController,
                           MPPI_CONTROLLER_COLORED, CartpoleDynamicsParams,

@@ -12,6 +12,19 @@ from . import buildlib as _build
 
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 
+# enum mppi_status
+MPPI_OK = 0
+MPPI_ERR_INVALID_ARG = 1
+MPPI_ERR_UNKNOWN_MODEL = 2
+MPPI_ERR_NO_DEVICE = 3
+MPPI_ERR_HIP = 4
+MPPI_ERR_LAUNCH_SHAPE = 5
+MPPI_ERR_LDS_OVERFLOW = 6
+MPPI_ERR_STATE = 7
+MPPI_ERR_NAN = 8
+MPPI_ERR_COMM = 9
+MPPI_ERR_UNSUPPORTED = 10
+
 
 class MppiConfig(C.Structure):
     """struct mppi_config"""

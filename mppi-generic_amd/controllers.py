@@ -9,7 +9,8 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import MppiConfig, MppiGaussianParams, MppiLaunchInfo, MppiStats, load_library
+from .capi import (MPPI_ERR_INVALID_ARG, MPPI_ERR_UNKNOWN_MODEL, MppiConfig, MppiGaussianParams, MppiLaunchInfo, MppiStats,
+                   load_library)
 
 MPPI_CONTROLLER_VANILLA = 0
 MPPI_CONTROLLER_TUBE = 1
@@ -20,7 +21,6 @@ MPPI_NOISE_INJECTED = 1
 MPPI_NOISE_ROCRAND_HOST = 2
 MPPI_KERNEL_AUTO, MPPI_KERNEL_FUSED, MPPI_KERNEL_PIPELINE = 0, 1, 2
 MPPI_REDUCTION_FUSED, MPPI_REDUCTION_REFERENCE_ORDER, MPPI_REDUCTION_REFERENCE_ORDER_FMA = 0, 1, 2
-MPPI_ERR_INVALID_ARG = 1
 
 
 class MPPIError(RuntimeError):
@@ -710,7 +710,7 @@ def describe_model(name, sampler_kind=MPPI_SAMPLER_GAUSSIAN):
     lib = load_library()
     n, caps = C.c_int(), C.c_uint()
     st = lib.mppi_describe_model(name.encode(), sampler_kind, None, 0, C.byref(n), C.byref(caps))
-    if st == 2:  # MPPI_ERR_UNKNOWN_MODEL
+    if st == MPPI_ERR_UNKNOWN_MODEL:
         return None
     _op_check(lib, st)
     buf = (C.c_int * (4 * n.value))()

@@ -5,7 +5,9 @@ import numpy as np
 import mppi_generic_amd as m
 import pyoracle as po
 
-SEED = 42
+SEED = 42          # the host generators and every handle's creation seed
+PHILOX_SEED = 77   # setSeed() of the in-kernel Philox stream in the kernel-form files
+U_TOL = 1e-5       # the project's standing bar on u* against the oracle
 
 
 def cartpole_cfg(K=2048, T=100, lambda_=0.25, num_iters=1, soft=False):
@@ -180,3 +182,87 @@ def merge_records_numpy(U, rho, eta, lambda_):
     s = np.exp(-(rho - rho_min) / lambda_)
     eta_tot = float((s * eta).sum())
     return (s[:, None] * U).sum(0) / eta_tot, rho_min, eta_tot
+
+
+# ---- small configurations and scenarios that several test files and tools share -----------------------------------------
+def robust_cfg(K=1024, T=50, tube=False, num_iters=1):
+    cfg = di_cfg(K=K, T=T, tube=tube, num_iters=num_iters)
+    cfg["model"] = "double_integrator_robust"
+    cfg["cost"].crash_cost = 100  # double_integrator_CORL2020.cu:253, :431, :632
+    return cfg
+
+
+def colored_cartpole(K=1024, T=50, **kw):
+    cfg = cartpole_cfg(K=K, T=T, soft=True, **kw)
+    cfg["colored"] = ([1.0], 0.97, 0.0)
+    return cfg
+
+
+def tube_sticky_scenario(cfg, calls=8):
+    """the oracle's closed loop with independent per-system noise and a zero threshold; returns per call (x, eps) and whether the
+    call was of the kind the advisor found: the nominal system restarted from the actual state in an EARLIER pass of the call
+    and was kept by the last one (nominal_state_used = 1 although the nominal trajectory starts at x)"""
+    orc = make_oracle(cfg)
+    orc.set_independent_noise(True)
+    orc.set_controller_params(nominal_threshold=0.0)
+    x = cfg["x0"].copy()
+    out = []
+    for i in range(calls):
+        eps = np.stack([host_noise(cfg["num_iters"], cfg["K"], cfg["T"], 2, seed=100 + 2 * i + d) for d in range(2)], axis=1)
+        orc.tube_compute_control(x, 1, eps)
+        kept_after_takeover = orc.stats()["nominal_state_used"] == 1 and np.array_equal(orc.nominal_state_traj()[0], x)
+        out.append((x.copy(), eps, kept_after_takeover, orc.control().copy(), orc.nominal_control().copy(),
+                    orc.state_traj().copy(), orc.nominal_state_traj().copy(), orc.stats()["nominal_state_used"]))
+        orc.tube_slide(1)
+        x = x + np.array([0.05, -0.03, 0.2, -0.1], np.float32) * (1 + i % 3)
+    return out
+
+
+def rm_cfg(model="di", K=1024, T=40, num_iters=1):
+    """the Robust MPPI configurations of tests/test_rmppi.py"""
+    if model == "di":
+        cfg = di_cfg(K=K, T=T, tube=True, num_iters=num_iters)
+        cfg["control_cost_coeff"] = [0.3, 0.2]  # exercise the likelihood-ratio and feedback cost terms
+        cfg["ranges"] = [[-3.0, 3.0], [-3.0, 3.0]]
+    elif model == "racer":
+        cfg = racer_cfg(K=K, T=T, num_iters=num_iters)
+        cfg["D"] = 2
+        cfg["control_cost_coeff"] = [0.2, 0.1]
+    elif model in ("elevation", "lstm_steering", "suspension", "complete"):
+        from racer_cfgs import elevation_cfg, steering_cfg, suspension_cfg, uncertainty_cfg
+        mk = {"elevation": elevation_cfg, "lstm_steering": steering_cfg, "suspension": suspension_cfg, "complete": uncertainty_cfg}
+        cfg = mk[model](K=K, T=T, D=2)
+        cfg["num_iters"] = num_iters
+        cfg["control_cost_coeff"] = [0.2, 0.1]
+    elif model in ("autorally", "lstm"):
+        # the NN models: Robust MPPI runs them one lane per rollout and system (LDS forward)
+        cfg = autorally_cfg(K=K, T=T, num_iters=num_iters) if model == "autorally" else bicycle_lstm_cfg(K=K, T=T, num_iters=num_iters)
+        cfg["D"] = 2
+        cfg["control_cost_coeff"] = [0.2, 0.1]
+    else:
+        cfg = cartpole_cfg_lr(K=K, T=T)
+        cfg["D"] = 2
+        cfg["num_iters"] = num_iters
+        cfg["std_dev"] = [5.0, 4.0]  # different exploration for the nominal and the real system
+    return cfg
+
+
+def gains(T, S, C, seed=1, scale=0.4):
+    return np.random.default_rng(seed).uniform(-scale, scale, (T, S, C)).astype(np.float32)
+
+
+def make_pair(cfg, thr=1000.0, nc=9, ns=32, **kw):
+    eng = m.RobustMPPIController(cfg["model"], cfg["K"], cfg["T"], cfg["dt"], cfg["lambda_"], cfg["alpha"], cfg["num_iters"],
+                                 seed=SEED, **kw)
+    if cfg["dyn"] is not None:
+        eng.setDynamicsParams(cfg["dyn"])
+    eng.setCostParams(cfg["cost"])
+    for name, blob in cfg.get("blobs", {}).items():
+        eng.setModelBlob(name, blob)
+    if cfg["ranges"] is not None:
+        eng.setControlRanges(cfg["ranges"])
+    eng.setSamplingParams(cfg["std_dev"], cfg["control_cost_coeff"], cfg.get("pure_pct", 0.01), cfg.get("decay", 1.0))
+    eng.setRMPPIParams(thr, nc, ns)
+    orc = make_oracle(cfg)
+    rob = po.RobustOracle(orc, thr, nc, ns)
+    return eng, orc, rob

@@ -22,6 +22,20 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert set(m.SIGNATURES) <= set(declared), set(m.SIGNATURES) - set(declared)
 
 
+def test_status_codes_equal_the_header_enum():
+    """every enumerator of mppi_status in include/mppi_amd.h is a constant of the package, name for name and value for
+    value, and the package declares no status the header does not"""
+    txt = open(os.path.join(REPO, "include", "mppi_amd.h")).read()
+    body = re.search(r"typedef enum mppi_status\s*\{(.*?)\}\s*mppi_status;", txt, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    declared = {name: int(value) for name, value in re.findall(r"\b(MPPI_[A-Z_]+)\s*=\s*(-?\d+)", body)}
+    assert len(declared) == len(re.findall(r"\bMPPI_[A-Z_]+\b", body)) >= 11  # (every enumerator carries its value)
+    from mppi_generic_amd import capi
+    for mod in (m, capi):
+        have = {k: v for k, v in vars(mod).items() if k == "MPPI_OK" or k.startswith("MPPI_ERR_")}
+        assert have == declared, (mod.__name__, sorted(set(have) ^ set(declared)), have, declared)
+
+
 def test_library_is_in_tree_and_gfx950(lib):
     path = m.library_path()
     assert path.startswith(REPO) and os.path.exists(path)
@@ -37,7 +51,7 @@ def test_no_cpu_fallback_without_device(lib):
     try:
         m.VanillaMPPIController("cartpole", 128, 10, 0.02, 1.0)
     except m.MPPIError as e:
-        assert e.status == 3
+        assert e.status == m.MPPI_ERR_NO_DEVICE
     else:
         raise AssertionError("mppi_create succeeded without a device")
 

@@ -29,11 +29,10 @@ import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import autorally_cfg, cartpole_cfg, host_noise, make_engine, make_oracle, ulp_diff
+from common import U_TOL, autorally_cfg, cartpole_cfg, host_noise, make_engine, make_oracle, ulp_diff
 
 pytestmark = pytest.mark.gpu
 
-U_TOL = 1e-5
 STEPS = 100
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

@@ -7,7 +7,8 @@ import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import (bicycle_lstm_cfg, cartpole_cfg, di_cfg, host_spectrum, make_engine, make_oracle, ulp_diff)
+from common import (bicycle_lstm_cfg, cartpole_cfg, colored_cartpole, di_cfg, host_spectrum, make_engine, make_oracle,
+                    ulp_diff)
 
 
 def _numpy_reference(z, exponents, decay, fmin, offset_t):
@@ -128,10 +129,8 @@ def test_philox_spectrum_is_standard_normal_and_shard_invariant():
 
 
 # ------------------------------------------------------------------ GPU ------------------------------------------------
-def _colored_cartpole(K=1024, T=50, **kw):
-    cfg = cartpole_cfg(K=K, T=T, soft=True, **kw)
-    cfg["colored"] = ([1.0], 0.97, 0.0)
-    return cfg
+def _colored_cartpole(K=1024, T=50, **kw):  # (a name of its own: it is part of the parametrised test ids)
+    return colored_cartpole(K=K, T=T, **kw)
 
 
 def _colored_bicycle(K=512, T=40, **kw):
@@ -254,11 +253,11 @@ def test_colored_mppi_params_argument_checks(gpu):
     eng = make_engine(_colored_cartpole(K=256, T=20))
     with pytest.raises(m.MPPIError) as e:
         eng.setColoredMPPIParams(gamma=10.0, r_exp=1.0)  # r = 1: division by zero in the exponent
-    assert e.value.status == 1
+    assert e.value.status == m.MPPI_ERR_INVALID_ARG
     van = m.VanillaMPPIController("cartpole", 128, 10, 0.02, 1.0)
     with pytest.raises(m.MPPIError) as e:
         van._check(van._lib.mppi_set_colored_mppi_params(van._h, 1.0, 2.0, None, 0, 1))
-    assert e.value.status == 7
+    assert e.value.status == m.MPPI_ERR_STATE
 
 
 @pytest.mark.gpu
@@ -287,4 +286,4 @@ def test_colored_params_rejected_on_gaussian_handle(gpu):
     c = m.VanillaMPPIController("cartpole", 128, 10, 0.02, 1.0)
     with pytest.raises(m.MPPIError) as e:
         c._check(c._lib.mppi_set_colored_noise_params(c._h, np.ones(1, np.float32), 0.9, 0.0))
-    assert e.value.status == 7
+    assert e.value.status == m.MPPI_ERR_STATE

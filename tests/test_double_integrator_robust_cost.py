@@ -13,16 +13,7 @@ import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import SEED, di_cfg, host_noise, make_engine, make_oracle, ulp_diff
-
-U_TOL = 1e-5
-
-
-def robust_cfg(K=1024, T=50, tube=False, num_iters=1):
-    cfg = di_cfg(K=K, T=T, tube=tube, num_iters=num_iters)
-    cfg["model"] = "double_integrator_robust"
-    cfg["cost"].crash_cost = 100  # double_integrator_CORL2020.cu:253, :431, :632
-    return cfg
+from common import di_cfg, host_noise, make_engine, make_oracle, robust_cfg, SEED, U_TOL, ulp_diff
 
 
 def _cost(oracle, s):

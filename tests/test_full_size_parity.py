@@ -17,12 +17,12 @@ import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import (autorally_cfg, bicycle_lstm_cfg, cartpole_cfg, di_cfg, host_noise, host_spectrum, make_engine,
+from common import (U_TOL, autorally_cfg, bicycle_lstm_cfg, cartpole_cfg, di_cfg, host_noise, host_spectrum, make_engine,
                     make_oracle, ulp_diff)
+from restate64 import bits
 
 pytestmark = pytest.mark.gpu
 
-U_TOL = 1e-5      # north_star: control-sequence L-inf vs reference
 ETA_RTOL = 1e-6
 X_TOL = 1e-4
 
@@ -246,10 +246,7 @@ def test_racer_elevation_16384x100_vs_oracle(gpu, model, block_y, variant):
     """The elevation-map RACER models (plain, LSTM steering, suspension, the complete model with the mean / uncertainty
     networks) over the synthetic hills at the size DESIGN.md §5 quotes (one block per CU): four lanes per rollout and one
     lane per rollout against the oracle, injected noise"""
-    from test_racer_dubins_elevation import elevation_cfg
-    from test_racer_dubins_lstm_steering import steering_cfg
-    from test_racer_dubins_lstm_unc import uncertainty_cfg
-    from test_racer_dubins_suspension import suspension_cfg
+    from racer_cfgs import elevation_cfg, steering_cfg, uncertainty_cfg, suspension_cfg
     cfg = {"elevation": elevation_cfg, "lstm_steering": steering_cfg, "suspension": suspension_cfg,
            "uncertainty": uncertainty_cfg}[model](K=16384, T=100)
     eng, orc = make_engine(cfg, block_x=64, block_y=block_y, kernel_variant=variant), make_oracle(cfg)
@@ -264,7 +261,7 @@ def test_suspension_two_systems_64x4x2_16384x100_vs_oracle(gpu):
     """Tube-MPPI on the suspension model with the (64, 4, 2) block — 512 threads, the instantiation that returned NaN costs for
     injected noise in round 2 while the steering weights sat in per-lane registers (csrc/models/
     racer_dubins_elevation_suspension.hip) — at the full size, injected noise, against the oracle"""
-    from test_racer_dubins_suspension import suspension_cfg
+    from racer_cfgs import suspension_cfg
     cfg = suspension_cfg(K=16384, T=100, D=2)
     eng, orc = make_engine(cfg, block_x=64, block_y=4), make_oracle(cfg)
     eps = host_noise(1, cfg["K"], cfg["T"], 2, seed=11)
@@ -281,10 +278,6 @@ def test_suspension_two_systems_64x4x2_16384x100_vs_oracle(gpu):
 
 
 # ------------------------------------------------------------------ Robust MPPI at the sizes bench.py times it ---------------
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def _robust_pair(cfg, thr, reference_order, nc=9, ns=32, **kw):
     eng = m.RobustMPPIController(cfg["model"], cfg["K"], cfg["T"], cfg["dt"], cfg["lambda_"], cfg["alpha"], cfg["num_iters"],
                                  seed=42, **kw)
@@ -335,8 +328,8 @@ def _robust_two_cycles(cfg, thr, reference_order, x_real, require_finite_candida
             if require_finite_candidates:
                 assert np.isfinite(fe_g).all(), fe_g
             if reference_order:
-                assert np.array_equal(_bits(fe_g), _bits(fe_o)), (fe_g, fe_o)
-                assert np.array_equal(_bits(ns_g), _bits(ns_o))
+                assert np.array_equal(bits(fe_g), bits(fe_o)), (fe_g, fe_o)
+                assert np.array_equal(bits(ns_g), bits(ns_o))
             else:
                 np.testing.assert_allclose(fe_g, fe_o, rtol=1e-5)
                 np.testing.assert_allclose(ns_g, ns_o, rtol=1e-5, atol=1e-6)
@@ -364,9 +357,9 @@ def _robust_two_cycles(cfg, thr, reference_order, x_real, require_finite_candida
         assert du <= U_TOL and dun <= U_TOL, (cycle, du, dun)
         assert np.abs(eng.getTargetStateSeq() - orc.nominal_state_traj()).max() <= X_TOL
         if reference_order:
-            assert np.array_equal(_bits(u_g), _bits(orc.control())), cycle
-            assert np.array_equal(_bits(un_g), _bits(orc.nominal_control())), cycle
-            assert np.array_equal(_bits(eng.getTargetStateSeq()), _bits(orc.nominal_state_traj())), cycle
+            assert np.array_equal(bits(u_g), bits(orc.control())), cycle
+            assert np.array_equal(bits(un_g), bits(orc.nominal_control())), cycle
+            assert np.array_equal(bits(eng.getTargetStateSeq()), bits(orc.nominal_state_traj())), cycle
         x = x_real.copy()
     eng.close()
 
@@ -392,7 +385,7 @@ def test_robust_complete_racer_4096x100_vs_oracle(gpu, variant):
     networks, covariance propagation, elevation / normals maps): the instantiation with the most spilled registers of the whole
     library (round 5's code object: 217-222 spilled VGPRs, 405-438 spilled SGPRs, 672-688 B of scratch per lane), at K = 4096,
     T = 100 — 64 blocks of 64 rollouts x 2 systems, past the K ~ 1000 the round-5 tests stopped at.  Both kernel structures."""
-    from test_racer_dubins_lstm_unc import uncertainty_cfg
+    from racer_cfgs import uncertainty_cfg
     cfg = uncertainty_cfg(K=4096, T=100, D=2)
     cfg["control_cost_coeff"] = [0.2, 0.1]
     dx = np.zeros_like(cfg["x0"])
@@ -412,8 +405,7 @@ def _robust_racer_bench_size(model):
     differs in the seventh digit, and on the suspension model at this size the real system's u* then lands 1.4e-5 away from
     the oracle's — a difference the reference-order run, which starts both cycles from identical inputs, does not show — so
     that cycle of the default reduction is compared for the complete model only."""
-    from test_racer_dubins_lstm_unc import uncertainty_cfg
-    from test_racer_dubins_suspension import suspension_cfg
+    from racer_cfgs import uncertainty_cfg, suspension_cfg
     cfg = {"complete": uncertainty_cfg, "suspension": suspension_cfg}[model](K=16384, T=100, D=2)
     cfg["control_cost_coeff"] = [0.2, 0.1]
     dx = np.zeros_like(cfg["x0"])

@@ -71,16 +71,16 @@ def test_weighted_reduction_kernel(gpu):
 def test_error_codes(gpu):
     with pytest.raises(m.MPPIError) as e:
         m.VanillaMPPIController("no_such_model", 128, 10, 0.02, 1.0)
-    assert e.value.status == 2 and "cartpole" in str(e.value)
+    assert e.value.status == m.MPPI_ERR_UNKNOWN_MODEL and "cartpole" in str(e.value)
     with pytest.raises(m.MPPIError) as e:  # launch shape not instantiated (reference: exit(), mppi_common.cu:1266-1277)
         m.VanillaMPPIController("cartpole", 128, 10, 0.02, 1.0, block_x=48, block_y=3)
-    assert e.value.status == 5
+    assert e.value.status == m.MPPI_ERR_LAUNCH_SHAPE
     # LDS overflow (reference: runtime_error, mppi_controller.cu:64-76).  Every rollout kernel moves its sample rows to HBM
     # when they do not fit (T = 2000 on the pipeline variant runs) and the post-processing kernels their control sequence
     # (tests/test_long_horizon.py: T = 25 000); what is left is the LDS + barrier variant of the post-processing kernel, which
     # collects its trajectories in LDS — a RACER model with a network of another shape than its four-lane form at T = 4000
     m.VanillaMPPIController("cartpole", 128, 2000, 0.02, 1.0, block_x=64, block_y=1, kernel_variant=2).close()
-    from test_racer_dubins_lstm_steering import steering_cfg
+    from racer_cfgs import steering_cfg
     from common import make_engine
     rng = np.random.default_rng(2)
     cfg = steering_cfg(K=128, T=4000)
@@ -93,18 +93,18 @@ def test_error_codes(gpu):
     big = make_engine(cfg)
     with pytest.raises(m.MPPIError) as e:
         big.computeControl(cfg["x0"], 1)
-    assert e.value.status == 6
+    assert e.value.status == m.MPPI_ERR_LDS_OVERFLOW
     big.close()
     with pytest.raises(m.MPPIError) as e:
         m.VanillaMPPIController("cartpole", 0, 10, 0.02, 1.0)
-    assert e.value.status == 1
+    assert e.value.status == m.MPPI_ERR_INVALID_ARG
     c = m.VanillaMPPIController("cartpole", 128, 10, 0.02, 1.0)
     with pytest.raises(m.MPPIError) as e:
         c.setDynamicsParams(m.DoubleIntegratorParams())  # wrong struct size
-    assert e.value.status == 1
+    assert e.value.status == m.MPPI_ERR_INVALID_ARG
     with pytest.raises(m.MPPIError) as e:
         c.getSampledControls()  # created without save_samples
-    assert e.value.status == 7
+    assert e.value.status == m.MPPI_ERR_STATE
 
 
 def test_nan_state_reports_error(gpu):
@@ -113,7 +113,7 @@ def test_nan_state_reports_error(gpu):
     eng = make_engine(cfg)
     with pytest.raises(m.MPPIError) as e:
         eng.computeControl(np.array([np.nan, 0, 0, 0], np.float32), 1)
-    assert e.value.status == 8
+    assert e.value.status == m.MPPI_ERR_NAN
 
 
 def test_two_way_sharding_on_one_gpu(gpu):
@@ -167,12 +167,12 @@ def test_rccl_exchange_path_on_one_gpu(gpu):
     lib = m.load_library()
     buf = C.create_string_buffer(128)
     nb = C.c_size_t()
-    assert lib.mppi_rccl_unique_id(buf, 128, C.byref(nb)) == 0 and nb.value == 128
+    assert lib.mppi_rccl_unique_id(buf, 128, C.byref(nb)) == m.MPPI_OK and nb.value == 128
     eng = make_engine(cfg, force_exchange=True)
     with pytest.raises(m.MPPIError) as e:  # exchange requested but no communicator yet
         eng.uploadState(cfg["x0"])
         eng.optimize(1)
-    assert e.value.status == 7
+    assert e.value.status == m.MPPI_ERR_STATE
     eng.setSeed(42)
     eng.commInitRccl(bytes(buf.raw))
     eng.uploadState(cfg["x0"])

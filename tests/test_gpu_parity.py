@@ -11,10 +11,10 @@ import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import (cartpole_cfg, cartpole_cfg_lr, di_cfg, host_noise, make_engine, make_oracle, ulp_diff)
+from common import (U_TOL, cartpole_cfg, cartpole_cfg_lr, di_cfg, host_noise, make_engine, make_oracle, tube_sticky_scenario,
+                    ulp_diff)
 
 pytestmark = pytest.mark.gpu
-U_TOL = 1e-5
 
 
 def _rollout_both(cfg, eps, mean=None, stride=1, **kw):
@@ -244,26 +244,6 @@ def test_tube_double_integrator_parity(gpu):
         x = x + np.array([0.05, -0.03, 0.2, -0.1], np.float32) * (i + 1)
 
 
-def _tube_sticky_scenario(cfg, calls=8):
-    """the oracle's closed loop with independent per-system noise and a zero threshold; returns per call (x, eps) and whether the
-    call was of the kind the advisor found: the nominal system restarted from the actual state in an EARLIER pass of the call
-    and was kept by the last one (nominal_state_used = 1 although the nominal trajectory starts at x)"""
-    orc = make_oracle(cfg)
-    orc.set_independent_noise(True)
-    orc.set_controller_params(nominal_threshold=0.0)
-    x = cfg["x0"].copy()
-    out = []
-    for i in range(calls):
-        eps = np.stack([host_noise(cfg["num_iters"], cfg["K"], cfg["T"], 2, seed=100 + 2 * i + d) for d in range(2)], axis=1)
-        orc.tube_compute_control(x, 1, eps)
-        kept_after_takeover = orc.stats()["nominal_state_used"] == 1 and np.array_equal(orc.nominal_state_traj()[0], x)
-        out.append((x.copy(), eps, kept_after_takeover, orc.control().copy(), orc.nominal_control().copy(),
-                    orc.state_traj().copy(), orc.nominal_state_traj().copy(), orc.stats()["nominal_state_used"]))
-        orc.tube_slide(1)
-        x = x + np.array([0.05, -0.03, 0.2, -0.1], np.float32) * (1 + i % 3)
-    return out
-
-
 @pytest.mark.parametrize("low_latency", [True, False], ids=["flags", "copies"])
 def test_tube_take_over_is_sticky_within_a_call(gpu, low_latency, monkeypatch):
     """num_iters = 2, independent noise per system, threshold 0, slide between the calls: when pass 0 restarts the nominal system
@@ -273,7 +253,7 @@ def test_tube_take_over_is_sticky_within_a_call(gpu, low_latency, monkeypatch):
     if not low_latency:
         monkeypatch.setenv("MPPI_AMD_NO_SPIN", "1")
     cfg = di_cfg(K=256, T=30, tube=True, num_iters=2)
-    rec = _tube_sticky_scenario(cfg)
+    rec = tube_sticky_scenario(cfg)
     assert any(r[2] for r in rec[:-1])
     eng = make_engine(cfg)
     eng.setIndependentNoise(True)

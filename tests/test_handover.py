@@ -1,31 +1,20 @@
 """The two hand-overs of mppi_compute_control give the same results: device-mapped host memory + flags (default: the call
 returns when the control sequence is out, the state trajectories follow behind it) and pinned copies + one stream
 synchronisation (MPPI_AMD_NO_SPIN=1, read when the handle is created).  Vanilla and Robust MPPI."""
-import os
 
 import numpy as np
 import pytest
 
 import mppi_generic_amd as m
-from common import cartpole_cfg, make_engine
-import test_rmppi as tr
+from common import cartpole_cfg, gains, make_engine, make_pair, rm_cfg
+from kernel_forms import env_override
 
 pytestmark = pytest.mark.gpu
 
 
 def _with_env(value, make):
-    old = os.environ.get("MPPI_AMD_NO_SPIN")
-    if value is None:
-        os.environ.pop("MPPI_AMD_NO_SPIN", None)
-    else:
-        os.environ["MPPI_AMD_NO_SPIN"] = value
-    try:
+    with env_override(MPPI_AMD_NO_SPIN=value):
         return make()
-    finally:
-        if old is None:
-            os.environ.pop("MPPI_AMD_NO_SPIN", None)
-        else:
-            os.environ["MPPI_AMD_NO_SPIN"] = old
 
 
 def test_vanilla_handovers_agree(gpu):
@@ -85,16 +74,16 @@ def test_tube_handovers_agree(gpu, num_iters):
 def test_robust_handovers_agree(gpu, model):
     """Robust MPPI: both control sequences and the statistics come back with the first flag of each system; the nominal
     state trajectory — the next updateImportanceSamplingControl builds its candidates from it — behind the second"""
-    cfg = tr._rm_cfg(model, K=1024, T=40, num_iters=2)
+    cfg = rm_cfg(model, K=1024, T=40, num_iters=2)
     out = []
     for env in (None, "1"):
-        eng, orc, rob = _with_env(env, lambda: tr._make_pair(cfg, thr={"di": 25.0}.get(model, 500.0)))
+        eng, orc, rob = _with_env(env, lambda: make_pair(cfg, thr={"di": 25.0}.get(model, 500.0)))
         S, C, T = eng.STATE_DIM, eng.CONTROL_DIM, cfg["T"]
         x = cfg["x0"].copy()
         rec = []
         for i in range(4):
             eng.updateImportanceSamplingControl(x, 1)
-            eng.setFeedbackGains(tr._gains(T, S, C, seed=10 + i, scale=0.3))
+            eng.setFeedbackGains(gains(T, S, C, seed=10 + i, scale=0.3))
             eng.computeControl(x, 1)
             st = eng.getStats()
             r = [eng.getControlSeq().copy(), eng.getNominalControlSeq().copy(),

@@ -41,140 +41,23 @@ Constraints: every registered model keeps the base Dynamics::enforceConstraints 
 ranges: dynamics.cu:97-116; no model overrides it, the configurations set no deadband), so constrain64 is a numpy clip for all
 of them and none needs the oracle's model code.  ColoredMPPI clamps control channel 1 only (constrain_mode 1).
 """
-import os
-
 import numpy as np
 import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import host_noise, host_spectrum, ulp_diff
-from test_kernel_matrix import BUILDERS, _make, _registrations, build_cases
+from common import PHILOX_SEED, U_TOL, di_cfg, host_noise, host_spectrum, ulp_diff
+from kernel_forms import (BUILDERS, FUSED_DRIFT, build_cases, expects_streamed_merge, make_handles, registrations,
+                          robust_gains)
+from restate64 import (SG_TAPS, SOFTMIN_RTOL, bits_equal, constrain64, ranges, save_history64, slide64, smooth64, softmin64,
+                       stats64, stats_of)
 
 N_CALLS = 3
 N_ITERS = 3
 STRIDES = (1, 2, 1)  # optimisation stride of call c; calls 1 and 2 are preceded by a slide / plant advance of that many steps
 PHILOX_KT = (1049, 12)
 INJECTED_KT = (200, 9)
-SEED = 77
-U_TOL = 1e-5
 NORM_RTOL_ORACLE = 1e-6
-SOFTMIN_RTOL = 2e-6
-EPS32 = float(np.finfo(np.float32).eps)  # 2^-23
-MPPI_ERR_INVALID_ARG = 1
-
-# ------------------------------------------------------------------ float64 restatements (numpy only) ------------------
-def softmin64(costs, v, lambda_):
-    """u* = sum_k w_k v_k / sum_k w_k, w_k = exp(-(c_k - min c) / lambda), in float64"""
-    c = np.asarray(costs, np.float64)
-    w = np.exp(-(c - c.min()) / lambda_)
-    return (w[:, None, None] * np.asarray(v, np.float64)).sum(0) / w.sum()
-
-
-def stats64(costs, lambda_):
-    """core/mppi_common.cu:1065-1081 evaluated in float64 on fp32 costs -> (values, bounds), both dicts with the keys
-    baseline, normalizer, free_energy_mean, free_energy_variance, free_energy_modified_variance.
-
-    The bounds are first-order fp32 rounding bounds, computed from K, u = 2^-24 and the costs themselves.  Weight k has the
-    argument x_k = (c_k - b) / lambda; the engine forms it as fl(fl(c_k - b) * fl(1 / lambda)) (3 roundings: relative 3u,
-    so 3u x_k absolute in the exponent) and det::exp adds <= 2 ulp = 4u, so w_k carries d_k = 3u x_k + 4u relative.  Any
-    summation order of K positive terms adds at most (K - 1) u relative (Higham, Accuracy and Stability, 4.2), and the
-    division by K one more u:
-      e1 = sum w_k d_k / sum w_k + K u                       relative error of m  = mean w
-      e2 = sum w_k^2 (2 d_k + u) / sum w_k^2 + K u           relative error of m2 = mean w^2 (one more rounding: the square)
-    and then
-      baseline   = min c                exact (a minimum of fp32 values is one of them)
-      normalizer = K m                  2e-6 relative (the reference accumulates in double: only the weights round, e1 - K u)
-      fe  = -lambda log m + b           lambda e1 + 8u (lambda |log m| + |b|): m's relative error becomes an absolute one
-                                        through the log; log (2 ulp), the product and the sum round
-      var = lambda (m2 - m^2)           lambda (e2 m2 + (2 e1 + u) m^2) + 3u |var|: m2 and m^2 carry their own relative
-                                        errors and cancel, so the bound is relative to the operands, not to the difference
-      mod = lambda (q + q^2 / 2), q = var / (m sqrt K)
-                                        lambda (1 + |q|) dq + 4u |mod|, dq = d_var / (m sqrt K) + |q| (e1 + 6u)
-    """
-    c = np.asarray(costs, np.float32).astype(np.float64)
-    K = c.size
-    u = EPS32 / 2
-    b = c.min()
-    x = (c - b) / lambda_
-    w = np.exp(-x)
-    d = 3 * u * x + 4 * u
-    e1 = (w * d).sum() / w.sum() + K * u
-    e2 = (w * w * (2 * d + u)).sum() / (w * w).sum() + K * u
-    mean, mean2 = w.mean(), (w * w).mean()
-    fe = -lambda_ * np.log(mean) + b
-    var = lambda_ * (mean2 - mean * mean)
-    q = var / (mean * np.sqrt(K))
-    mod = lambda_ * (q + 0.5 * q * q)
-    d_fe = lambda_ * e1 + 8 * u * (lambda_ * abs(np.log(mean)) + abs(b))
-    d_var = lambda_ * (e2 * mean2 + (2 * e1 + u) * mean * mean) + 3 * u * abs(var)
-    d_q = d_var / (mean * np.sqrt(K)) + abs(q) * (e1 + 6 * u)
-    d_mod = lambda_ * (1 + abs(q)) * d_q + 4 * u * abs(mod)
-    vals = dict(baseline=b, normalizer=w.sum(), free_energy_mean=fe, free_energy_variance=var,
-                free_energy_modified_variance=mod)
-    bounds = dict(baseline=0.0, normalizer=SOFTMIN_RTOL * w.sum(), free_energy_mean=d_fe, free_energy_variance=d_var,
-                  free_energy_modified_variance=d_mod)
-    return vals, bounds
-
-
-SG_TAPS = np.array([-3.0, 12.0, 17.0, 12.0, -3.0]) / 35.0
-
-
-def smooth64(u, history):
-    """controller.cuh:557-586: the 5-tap Savitzky-Golay filter over [hist0, hist1, u_0 .. u_{T-1}, u_{T-1}, u_{T-1}] ->
-    (smoothed [T][C] in float64, bound [T][C]).  The engine filters in fp32 with the taps divided by 35 first: every tap, every
-    product and each of the four additions rounds once, sum |tap_j| = 47/35 < 1.35, so the error is below
-    (1 + 5 + 4) u 1.35 max|input| < 8 * 2^-23 * max|input| over the five inputs of the window (u = 2^-24)."""
-    u = np.asarray(u, np.float64)
-    T, C = u.shape
-    buf = np.concatenate([np.asarray(history, np.float64).reshape(2, C), u, u[-1:], u[-1:]])
-    out = np.zeros((T, C))
-    peak = np.zeros((T, C))
-    for j in range(5):
-        out += SG_TAPS[j] * buf[j:j + T]
-        peak = np.maximum(peak, np.abs(buf[j:j + T]))
-    return out, 8 * EPS32 * peak
-
-
-def slide64(u, steps, zero=None, scale=None):
-    """controller.cuh:588-600 (the engine's default slide scale is 0: the tail is the zero control)"""
-    u = np.asarray(u, np.float64)
-    T, C = u.shape
-    zero = np.zeros(C) if zero is None else np.asarray(zero, np.float64)
-    scale = np.zeros(C) if scale is None else np.asarray(scale, np.float64)
-    out = np.empty_like(u)
-    for i in range(T):
-        src = u[min(i + steps, T - 1)]
-        out[i] = (src - zero) * scale + zero if i + steps > T - 1 else src
-    return out
-
-
-def save_history64(steps, u, history):
-    """controller.cuh:602-615: history [2][C] (row 0 older) after a slide of `steps` of the control sequence u"""
-    h = np.array(history, np.float64).reshape(2, -1)
-    u = np.asarray(u, np.float64)
-    if steps == 1:
-        h = np.stack([h[1], u[0]])
-    elif steps >= 2:
-        h = np.stack([u[steps - 2], u[steps - 1]])
-    return h
-
-
-def constrain64(u, lo_hi, channels=None):
-    """the base Dynamics::enforceConstraints with no deadband: a clamp of every (or only the listed) control channel"""
-    u = np.array(u, np.float64)
-    lo, hi = lo_hi
-    ch = range(u.shape[1]) if channels is None else channels
-    for c in ch:
-        u[:, c] = np.minimum(np.maximum(u[:, c], lo[c]), hi[c])
-    return u
-
-
-def _ranges(cfg, C):
-    if cfg["ranges"] is None:
-        return np.full(C, -np.inf), np.full(C, np.inf)
-    r = np.asarray(cfg["ranges"], np.float64).reshape(C, 2)
-    return r[:, 0], r[:, 1]
 
 
 # ------------------------------------------------------------------ cases -----------------------------------------------
@@ -182,18 +65,8 @@ def _control_dim(model):
     return len(BUILDERS[model](1, 1, 1)["std_dev"])
 
 
-def expects_streamed_merge(case, d, K, T, C, philox, reduction_fused=True):
-    """streamMergeApplies() (engine_iteration.hip) for this case's handle: the one-system role pipeline at 64x1x1 with its
-    sample rows in LDS, in-kernel Philox noise, the fused reduction, no Tsallis weights (no case sets them), not Robust,
-    T*C % 4 == 0, at most 256 blocks, and a model that supports it"""
-    e = case["expect"]
-    return bool(philox and reduction_fused and e["family"] == "pipeline" and e["block"] == (64, 1, 1) and not e["rows_in_hbm"]
-                and case["controller"] in ("vanilla", "colored") and (T * C) % 4 == 0 and -(-K // 64) <= 256
-                and d["streamed_merge"])
-
-
 def sequence_cases():
-    regs = {(n, s): d for n, s, d in _registrations()}
+    regs = {(n, s): d for n, s, d in registrations()}
     dims = {}
     out = []
     for case in build_cases():
@@ -217,7 +90,7 @@ def test_every_streamed_merge_registration_has_a_streamed_case(lib):
     Philox sequence expects the streamed merge — else the STREAM_MERGE instantiation of its rolloutPipelineKernel is never run"""
     cases = sequence_cases()
     assert len(cases) == len([c for c in build_cases() if not c["refuse"]])
-    for name, sampler, d in _registrations():
+    for name, sampler, d in registrations():
         if not (d["pipeline"] and d["streamed_merge"]):
             continue
         prefix = name + ("[colored]" if sampler else "") + "-"
@@ -355,50 +228,10 @@ def test_constrain64():
 
 
 # ------------------------------------------------------------------ GPU ------------------------------------------------
-def _bits_equal(a, b):
-    """bit for bit, NaN equal to NaN (some RACER outputs are NaN at t = 0)"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
-
-
-def _stats_of(stats, sysname):
-    s = getattr(stats, sysname)
-    return dict(baseline=s.baseline, normalizer=s.normalizer, free_energy_mean=s.free_energy_mean,
-                free_energy_variance=s.free_energy_variance, free_energy_modified_variance=s.free_energy_modified_variance)
-
-
-# Fused (default) handles whose control drifts past U_TOL from the oracle within the 3 calls, while the reference-order
-# handle of the same sequence stays within it: the fused merge sums the weighted samples in another order than the
-# reference, each iteration starts from the previous one's u*, and the difference grows over 9 iterations through the RACER
-# dynamics (the Tube nominal control, which is re-optimised from its own smoothed past, most of all).  Every other check of
-# these handles — path, launch counts, float64 softmin / statistics / smoothing, trajectories — holds unchanged.
-# (case id, sequence) -> bound: the largest control / nominal control difference measured over the 3 calls, rounded up.
-FUSED_DRIFT = {
-    ("racer_dubins-tube-fused16x1x2", "injected"): 1.3e-5,                         # measured 1.283e-5
-    ("racer_dubins-tube-auto-fold", "injected"): 1.35e-5,                          # measured 1.313e-5
-    ("racer_dubins_elevation_lstm_steering-robust-fused32x1x2", "philox"): 1.15e-5,  # measured 1.109e-5
-    ("racer_dubins_elevation_lstm_unc-tube-fused64x1x2", "injected"): 1.3e-5,      # measured 1.252e-5
-    ("racer_dubins_elevation_suspension-tube-fused64x4x2", "philox"): 1.05e-5,     # measured 1.031e-5
-    ("racer_dubins_elevation_suspension-tube-fused64x1x2", "philox"): 1.05e-5,     # measured 1.031e-5
-    ("racer_dubins_elevation_suspension-tube-fused64x4x2-hbm", "philox"): 1.05e-5,  # measured 1.031e-5
-    ("racer_dubins_elevation_suspension-tube-fused64x4x2", "injected"): 1.4e-5,    # measured 1.360e-5
-    ("racer_dubins_elevation_suspension-tube-fused64x1x2", "injected"): 1.4e-5,    # measured 1.360e-5
-    ("racer_dubins_elevation_suspension-tube-fused64x4x2-hbm", "injected"): 1.4e-5,  # measured 1.360e-5
-}
-
-
 def _fused_pair(case, K, T):
     """(streamed handle, two-launch twin) in the default fused reduction; MPPI_AMD_NO_STREAM_MERGE is read at mppi_create"""
-    _, streamed, _, _ = _make(case, K, T, num_iters=N_ITERS)
-    old = os.environ.get("MPPI_AMD_NO_STREAM_MERGE")
-    os.environ["MPPI_AMD_NO_STREAM_MERGE"] = "1"
-    try:
-        _, twin, _, _ = _make(case, K, T, num_iters=N_ITERS)
-    finally:
-        if old is None:
-            del os.environ["MPPI_AMD_NO_STREAM_MERGE"]
-        else:
-            os.environ["MPPI_AMD_NO_STREAM_MERGE"] = old
+    _, streamed, _, _ = make_handles(case, K, T, num_iters=N_ITERS)
+    _, twin, _, _ = make_handles(case, K, T, num_iters=N_ITERS, env=dict(MPPI_AMD_NO_STREAM_MERGE="1"))
     return streamed, twin
 
 
@@ -406,7 +239,7 @@ def _observe(eng, ctl, has_outputs):
     """everything a call hands back, for the streamed / two-launch comparison"""
     st = eng.getStats()
     out = dict(u=eng.getControlSeq(), u_opt=eng.getOptimalControlSeq(), costs=eng.getSampledCostSeq(),
-               x=eng.getTargetStateSeq(), stats=np.array(list(_stats_of(st, "real_sys").values()), np.float32))
+               x=eng.getTargetStateSeq(), stats=np.array(list(stats_of(st, "real_sys").values()), np.float32))
     if has_outputs:
         out["y"] = eng.getTargetOutputSeq()
     return out
@@ -469,7 +302,7 @@ def _check_handle(h, case, cfg, orc, x, call, tag, exact):
     sysnames = (["nominal_sys", "real_sys"] if ctl == "robust" else ["real_sys", "nominal_sys"])[:e.num_systems]
     if exact:
         for z, name in enumerate(sysnames):
-            s = _stats_of(st, name)
+            s = stats_of(st, name)
             assert s["baseline"] == ost["baseline"][z], "%s: %s baseline %r, oracle %r" % (tag, name, s["baseline"],
                                                                                           ost["baseline"][z])
             rn = abs(s["normalizer"] - ost["normalizer"][z]) / abs(ost["normalizer"][z])
@@ -483,7 +316,7 @@ def _check_handle(h, case, cfg, orc, x, call, tag, exact):
     for z, name in enumerate(sysnames):
         if ctl == "tube" and z == 1 and st.nominal_state_used == 0:
             # tubeSelectKernel: the actual system won the last pass, the nominal mean IS the actual one
-            assert _bits_equal(u_opt[1], u_opt[0]), "%s: nominal u* after a take-over" % tag
+            assert bits_equal(u_opt[1], u_opt[0], nan_equal=True), "%s: nominal u* after a take-over" % tag
         else:
             # Robust: row 0 of the dumped costs is the combined S_nom the nominal update weighs (rmppi_kernels.hpp)
             want = softmin64(costs[z], v[z], lam)
@@ -491,13 +324,13 @@ def _check_handle(h, case, cfg, orc, x, call, tag, exact):
             bound = SOFTMIN_RTOL * max(1.0, float(np.abs(want).max()))
             assert err <= bound, "%s: system %d u* is %g from the float64 softmin of its own samples" % (tag, z, err)
         want, bound = stats64(costs[z], lam)
-        got = _stats_of(st, name)
+        got = stats_of(st, name)
         for k in want:
             assert abs(got[k] - want[k]) <= bound[k], "%s: %s %s = %r, float64 %r (bound %g)" % (
                 tag, name, k, got[k], want[k], bound[k])
 
     # smoothing (and constraints) of what the call hands back, from u* and the history kept here
-    lo_hi = _ranges(cfg, C)
+    lo_hi = ranges(cfg, C)
     if ctl in ("vanilla", "colored"):
         sm, b = smooth64(u_opt[0], h.hist)
         want = sm if (ctl == "colored" and C == 1) else constrain64(sm, lo_hi, [1] if ctl == "colored" else None)
@@ -520,20 +353,20 @@ def _check_handle(h, case, cfg, orc, x, call, tag, exact):
     if ctl == "robust":
         # getTargetStateSeq is the nominal trajectory there, from the nominal state the candidates chose
         x0_n = e.getRMPPIState()[0]
-        assert _bits_equal(x_state, orc.state_trajectory(x0_n, un)), "%s: nominal state trajectory" % tag
-        assert _bits_equal(e.getNominalStateSeq(), x_state), tag
+        assert bits_equal(x_state, orc.state_trajectory(x0_n, un), nan_equal=True), "%s: nominal state trajectory" % tag
+        assert bits_equal(e.getNominalStateSeq(), x_state, nan_equal=True), tag
         traj_x0, traj_u = x0_n, un
     else:
-        assert _bits_equal(x_state, orc.state_trajectory(x, u)), "%s: state trajectory of the handed-back control" % tag
+        assert bits_equal(x_state, orc.state_trajectory(x, u), nan_equal=True), "%s: state trajectory of the handed-back control" % tag
         traj_x0, traj_u = x, u
     if O > 0:
         _, y = orc.output_trajectory(traj_x0, traj_u)
-        assert _bits_equal(e.getTargetOutputSeq(), y), "%s: output trajectory" % tag
+        assert bits_equal(e.getTargetOutputSeq(), y, nan_equal=True), "%s: output trajectory" % tag
     if ctl == "tube":
         xn = e.getNominalStateSeq()
         if exact:
-            assert _bits_equal(xn[0], orc.nominal_state_traj()[0]), "%s: nominal initial state" % tag
-        assert _bits_equal(xn, orc.state_trajectory(xn[0], un)), "%s: nominal state trajectory" % tag
+            assert bits_equal(xn[0], orc.nominal_state_traj()[0], nan_equal=True), "%s: nominal initial state" % tag
+        assert bits_equal(xn, orc.state_trajectory(xn[0], un), nan_equal=True), "%s: nominal state trajectory" % tag
     h.u, h.un = u, un
 
 
@@ -550,7 +383,7 @@ def _run_sequence(case, mode):
     K, T = PHILOX_KT if philox else INJECTED_KT
     ctl = case["controller"]
     tag0 = "%s %s K=%d T=%d" % (case["id"], mode, K, T)
-    cfg, eng, orc, rob = _make(case, K, T, num_iters=N_ITERS)
+    cfg, eng, orc, rob = make_handles(case, K, T, num_iters=N_ITERS)
     C, S, O = eng.CONTROL_DIM, eng.STATE_DIM, eng.OUTPUT_DIM
     handles = [_Handle(eng, "reference-order", False, C)]
     eng.setReductionMode(m.MPPI_REDUCTION_REFERENCE_ORDER)
@@ -559,18 +392,18 @@ def _run_sequence(case, mode):
             streamed, twin = _fused_pair(case, K, T)
             handles += [_Handle(streamed, "fused, streamed", True, C), _Handle(twin, "fused, two-launch", False, C)]
         else:
-            handles.append(_Handle(_make(case, K, T, num_iters=N_ITERS)[1], "fused", False, C))
+            handles.append(_Handle(make_handles(case, K, T, num_iters=N_ITERS)[1], "fused", False, C))
         engines = [h.e for h in handles]
         assert C == case["C"], tag0
         if ctl == "colored":
             exps, decay, fmin = cfg["colored"]
         if ctl == "robust":
-            gains = np.random.default_rng(5).uniform(-0.3, 0.3, (T, S, C)).astype(np.float32)
+            gains = robust_gains(T, S, C)
         for h in handles:
             h.counts0 = h.e.launchCounts()
         if philox:
             for e in engines:
-                e.setSeed(SEED)
+                e.setSeed(PHILOX_SEED)
         gen = 0  # the engine's h->generation, as worked out from launchRollout / rmNominalStateAndStride
         x = cfg["x0"].copy()
         for call in range(N_CALLS):
@@ -596,10 +429,10 @@ def _run_sequence(case, mode):
                 for e in engines:
                     e.injectNoise(z if ctl == "colored" else slabs)
             elif ctl == "colored":
-                z = np.stack([po.philox_spectrum(SEED, gen + i, K, T, C) for i in range(N_ITERS)])
+                z = np.stack([po.philox_spectrum(PHILOX_SEED, gen + i, K, T, C) for i in range(N_ITERS)])
 
             def draw(g):
-                return po.philox_normal(SEED, g, K, T, C) if philox else slabs[g % N_ITERS]
+                return po.philox_normal(PHILOX_SEED, g, K, T, C) if philox else slabs[g % N_ITERS]
 
             if ctl == "robust":
                 # updateImportanceSamplingControl: candidate evaluation (one generation; none on the first cycle) and slide
@@ -618,8 +451,8 @@ def _run_sequence(case, mode):
                 ns_o, best_o, nstride_o, fe_o = rob.state()
                 assert (best_e, nstride_e) == (best_o, nstride_o), "%s: best candidate / stride %s, oracle %s" % (
                     tag, (best_e, nstride_e), (best_o, nstride_o))
-                assert _bits_equal(ns_e, ns_o), "%s: nominal state %s, oracle %s" % (tag, ns_e, ns_o)
-                assert _bits_equal(fe_e, fe_o), "%s: candidate free energies %s, oracle %s" % (tag, fe_e, fe_o)
+                assert bits_equal(ns_e, ns_o, nan_equal=True), "%s: nominal state %s, oracle %s" % (tag, ns_e, ns_o)
+                assert bits_equal(fe_e, fe_o, nan_equal=True), "%s: candidate free energies %s, oracle %s" % (tag, fe_e, fe_o)
                 if call > 0:
                     for h in handles:  # (each handle's own candidate choice decides its nominal slide)
                         h.nhist = save_history64(h.e.getRMPPIState()[2], h.un, h.nhist)
@@ -645,7 +478,7 @@ def _run_sequence(case, mode):
             if len(handles) == 3:
                 a, b = _observe(handles[1].e, ctl, O > 0), _observe(handles[2].e, ctl, O > 0)
                 for k in a:
-                    assert _bits_equal(a[k], b[k]), "%s: %s of the streamed handle differs from the two-launch twin" % (tag, k)
+                    assert bits_equal(a[k], b[k], nan_equal=True), "%s: %s of the streamed handle differs from the two-launch twin" % (tag, k)
         bound = FUSED_DRIFT.get((case["id"], mode), U_TOL)
         for h in handles[1:]:
             assert h.drift <= bound, "%s [%s]: control differs from the oracle by up to %g over the %d calls (bound %g)" % (
@@ -667,7 +500,6 @@ def test_kernel_sequence(gpu, case):
 def test_compute_control_refuses_a_state_of_the_wrong_size(gpu, controller):
     """mppi_compute_control reads STATE_DIM floats for every controller; any other size is MPPI_ERR_INVALID_ARG, never a
     read of the staging array's stale tail (short state) or a silently dropped one (long state)"""
-    from common import di_cfg
     cfg = di_cfg(K=256, T=8, tube=controller is not m.VanillaMPPIController)
     eng = controller(cfg["model"], cfg["K"], cfg["T"], cfg["dt"], cfg["lambda_"])
     try:
@@ -675,12 +507,12 @@ def test_compute_control_refuses_a_state_of_the_wrong_size(gpu, controller):
         for n in (0, S - 1, S + 1, 2 * S + 1, 2 * S):
             with pytest.raises(m.MPPIError) as e:
                 eng.computeControl(np.ones(n, np.float32), 1)
-            assert e.value.status == MPPI_ERR_INVALID_ARG, (n, e.value.status)
+            assert e.value.status == m.MPPI_ERR_INVALID_ARG, (n, e.value.status)
         if controller is m.RobustMPPIController:  # updateImportanceSamplingControl reads a state of STATE_DIM floats too
             for n in (0, S - 1, S + 1, 2 * S + 1, 2 * S):
                 with pytest.raises(m.MPPIError) as e:
                     eng.updateImportanceSamplingControl(np.ones(n, np.float32), 1)
-                assert e.value.status == MPPI_ERR_INVALID_ARG, (n, e.value.status)
+                assert e.value.status == m.MPPI_ERR_INVALID_ARG, (n, e.value.status)
             eng.updateImportanceSamplingControl(np.ones(S, np.float32), 1)
         else:  # (Robust needs its gains first)
             eng.computeControl(np.ones(S, np.float32), 1)

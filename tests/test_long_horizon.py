@@ -1,6 +1,5 @@
 """Horizons whose sample rows do not fit the LDS: the rows-in-HBM form of the fused rollout kernel (the reference keeps its
 samples in global memory always and has no horizon limit, sampling_distributions/sampling_distribution.cu:169-205)."""
-import os
 
 import numpy as np
 import pytest
@@ -8,16 +7,14 @@ import pytest
 import mppi_generic_amd as m
 import pyoracle as po
 from common import autorally_cfg, cartpole_cfg, cartpole_cfg_lr, di_cfg, host_noise, make_engine, make_oracle, ulp_diff
+from kernel_forms import env_override
 
 pytestmark = pytest.mark.gpu
 
 
 def _engine_with_hbm_rows(cfg, **kw):
-    os.environ["MPPI_AMD_ROWS_IN_HBM"] = "1"
-    try:
+    with env_override(MPPI_AMD_ROWS_IN_HBM="1"):
         return make_engine(cfg, **kw)
-    finally:
-        del os.environ["MPPI_AMD_ROWS_IN_HBM"]
 
 
 @pytest.mark.parametrize("mk", [lambda: cartpole_cfg_lr(K=1000, T=50), lambda: di_cfg(K=512, T=33, tube=True),
@@ -175,11 +172,8 @@ def test_rmppi_T1000_vs_oracle(gpu):
 
 
 def _engine_with_finalize_scratch(cfg, **kw):
-    os.environ["MPPI_AMD_FINALIZE_SCRATCH"] = "1"
-    try:
+    with env_override(MPPI_AMD_FINALIZE_SCRATCH="1"):
         return make_engine(cfg, **kw)
-    finally:
-        del os.environ["MPPI_AMD_FINALIZE_SCRATCH"]
 
 
 @pytest.mark.parametrize("mk", [lambda: cartpole_cfg(K=512, T=60, soft=True), lambda: di_cfg(K=512, T=33, tube=True),

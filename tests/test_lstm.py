@@ -5,6 +5,7 @@ import pytest
 import mppi_generic_amd as m
 import pyoracle as po
 from common import bicycle_lstm_cfg, host_noise, lstm_npz, make_engine, make_oracle, ulp_diff
+from kernel_forms import env_override
 
 
 # ------------------------------------------------------------------ CPU: oracle pinned on the reference's KATs --------
@@ -126,31 +127,26 @@ def test_bicycle_lstm_requires_blobs(gpu):
     c = m.VanillaMPPIController("bicycle_slip_lstm", 128, 10, 0.02, 1.0)
     with pytest.raises(m.MPPIError) as e:
         c.computeControl(np.zeros(7, np.float32), 1)
-    assert e.value.status == 7 and "lstm_weights" in str(e.value)
+    assert e.value.status == m.MPPI_ERR_STATE and "lstm_weights" in str(e.value)
     with pytest.raises(m.MPPIError) as e:
         c.setModelBlob("lstm_weights", np.zeros(10, np.float32))
-    assert e.value.status == 1
+    assert e.value.status == m.MPPI_ERR_INVALID_ARG
 
 
 @pytest.mark.gpu
 def test_trajectory_rerollout_wave_form_equals_mfma_form(gpu):
     """the re-rollout of u* runs on the one-rollout-per-wave form of the LSTM model (lane = gate row / neuron, lstm_wave.hpp);
     the replicated-lane MFMA form gives the same bits, and both agree with the oracle's state trajectory"""
-    import os
     cfg = bicycle_lstm_cfg(K=512, T=120)
     eps = host_noise(1, cfg["K"], cfg["T"], 2)
     got = []
     for form in (None, "rep"):
-        if form:
-            os.environ["MPPI_AMD_FINALIZE_FORM"] = form
-        try:
+        with env_override(MPPI_AMD_FINALIZE_FORM=form):
             eng = make_engine(cfg)
             eng.injectNoise(eps)
             eng.computeControl(cfg["x0"], 1)
             got.append((eng.getControlSeq().copy(), eng.getTargetStateSeq().copy(), eng.getTargetOutputSeq().copy()))
             eng.close()
-        finally:
-            os.environ.pop("MPPI_AMD_FINALIZE_FORM", None)
     for a, b in zip(*got):
         assert np.array_equal(a, b)
     orc = make_oracle(cfg)

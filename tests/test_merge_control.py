@@ -6,28 +6,22 @@ constrains and hands the control sequence over — read from the TRANSPOSED copy
 pinned here is that the fused launch is the SAME FUNCTION as combineKernel + finalizeKernel's control phase: control sequence,
 statistics, trajectories and the device-resident mean, bit for bit, and against the CPU oracle within the usual bound.
 """
-import os
 
 import numpy as np
 import pytest
 
 from common import cartpole_cfg, cartpole_cfg_lr, di_cfg, make_engine, make_oracle
+from restate64 import bits
+from kernel_forms import env_override
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _pair(cfg, **kw):
     """(handle whose control phase merges, handle with combineKernel + control phase); the switch is read at mppi_create"""
     fused = make_engine(cfg, **kw)
-    os.environ["MPPI_AMD_NO_MERGE_CONTROL"] = "1"
-    try:
+    with env_override(MPPI_AMD_NO_MERGE_CONTROL="1"):
         plain = make_engine(cfg, **kw)
-    finally:
-        del os.environ["MPPI_AMD_NO_MERGE_CONTROL"]
     return fused, plain
 
 
@@ -52,17 +46,17 @@ def test_merging_control_phase_equals_merge_then_control_phase(gpu, cfg):
     for step in range(5):
         a.computeControl(x, 1)
         b.computeControl(x, 1)
-        assert np.array_equal(_bits(a.getControlSeq()), _bits(b.getControlSeq())), step
-        assert np.array_equal(_bits(_stats(a)), _bits(_stats(b))), step
-        assert np.array_equal(_bits(a.getTargetStateSeq()), _bits(b.getTargetStateSeq())), step
+        assert np.array_equal(bits(a.getControlSeq()), bits(b.getControlSeq())), step
+        assert np.array_equal(bits(_stats(a)), bits(_stats(b))), step
+        assert np.array_equal(bits(a.getTargetStateSeq()), bits(b.getTargetStateSeq())), step
         x, _ = a.modelStep(x, a.getControlSeq()[0])
         a.slideControlSequence(1)
         b.slideControlSequence(1)
     # the device-resident mean and statistics (what mppi_optimize and the operators continue from) are the merged ones
     for e in (a, b):
         e.optimize(2)
-    assert np.array_equal(_bits(a.getControlSeq()), _bits(b.getControlSeq()))
-    assert np.array_equal(_bits(_stats(a)), _bits(_stats(b)))
+    assert np.array_equal(bits(a.getControlSeq()), bits(b.getControlSeq()))
+    assert np.array_equal(bits(_stats(a)), bits(_stats(b)))
     a.close()
     b.close()
 
@@ -85,22 +79,19 @@ def test_merging_control_phase_against_the_oracle(gpu):
 def test_handles_the_merging_control_phase_leaves_alone(gpu):
     """no split hand-over (MPPI_AMD_SPLIT_FINALIZE=0), T*C not a multiple of 4: combineKernel + finalize as before"""
     cfg = cartpole_cfg(K=2048, T=100, soft=True, num_iters=2)
-    os.environ["MPPI_AMD_SPLIT_FINALIZE"] = "0"
-    try:
+    with env_override(MPPI_AMD_SPLIT_FINALIZE="0"):
         unsplit = make_engine(cfg)
-    finally:
-        del os.environ["MPPI_AMD_SPLIT_FINALIZE"]
     fused = make_engine(cfg)
     for e in (unsplit, fused):
         e.computeControl(cfg["x0"], 1)
-    assert np.array_equal(_bits(unsplit.getControlSeq()), _bits(fused.getControlSeq()))
-    assert np.array_equal(_bits(_stats(unsplit)), _bits(_stats(fused)))
+    assert np.array_equal(bits(unsplit.getControlSeq()), bits(fused.getControlSeq()))
+    assert np.array_equal(bits(_stats(unsplit)), bits(_stats(fused)))
     unsplit.close()
     fused.close()
     cfg = cartpole_cfg(K=1024, T=37, soft=True, num_iters=2)
     a, b = _pair(cfg)
     for e in (a, b):
         e.computeControl(cfg["x0"], 1)
-    assert np.array_equal(_bits(a.getControlSeq()), _bits(b.getControlSeq()))
+    assert np.array_equal(bits(a.getControlSeq()), bits(b.getControlSeq()))
     a.close()
     b.close()

@@ -15,23 +15,18 @@ Two consecutive calls per parity case, so the generation counter advances.  The 
 (as the exact handle of tests/test_kernel_sequence.py): with the fused merge u* differs from the oracle's by rounding, the
 second call would sample around another mean and its costs could not be held to 0 ulp.
 """
-import os
+import functools
 
 import numpy as np
 import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import autorally_cfg, cartpole_cfg, cartpole_cfg_lr, di_cfg, host_noise, make_engine, make_oracle, ulp_diff
-from test_kernel_matrix import KT
+from common import SEED, U_TOL, autorally_cfg, cartpole_cfg, cartpole_cfg_lr, di_cfg, host_noise, make_engine, robust_cfg, ulp_diff
+from kernel_forms import KT, check_against_oracle, compute_once, make_handles
 
-SEED = 42
-U_TOL = 1e-5
 NLN = getattr(m, "MPPI_SAMPLER_NLN", 2)
 NLN_STREAM_BASE = 16
-MPPI_ERR_INVALID_ARG = 1
-MPPI_ERR_UNKNOWN_MODEL = 2
-MPPI_ERR_UNSUPPORTED = 10
 MPPI_NOISE_ROCRAND_HOST = 2
 
 assert {(1, 1), (63, 2), (65, 3), (1049, 9)} <= set(KT)
@@ -97,7 +92,6 @@ def _di(K, T, D):
 
 
 def _di_robust(K, T, D):
-    from test_double_integrator_robust_cost import robust_cfg
     cfg = robust_cfg(K=K, T=T, tube=True)
     cfg["std_dev"] = [0.7, 0.4]
     cfg["control_cost_coeff"] = [0.2, 0.1]
@@ -136,20 +130,7 @@ PARITY_CASES = [
 ]
 
 
-def _make(case, K, T, sampler=NLN, num_iters=1, **extra):
-    ctl = case["controller"]
-    D = 1 if ctl == "vanilla" else 2
-    cfg = case["build"](K, T, D)
-    cfg["D"] = D
-    cfg["num_iters"] = num_iters
-    kw = dict(case["kw"], sampler=sampler, save_samples=True, **extra)
-    if ctl == "robust":
-        from test_rmppi import _make_pair
-        nc, ns = (9, 32) if K >= 9 * 32 else (3, K // 3)
-        eng, orc, rob = _make_pair(cfg, nc=nc, ns=ns, **kw)
-    else:
-        eng, orc, rob = make_engine(cfg, tube=D == 2, **kw), make_oracle(cfg), None
-    return cfg, eng, orc, rob
+_make = functools.partial(make_handles, sampler=NLN)
 
 
 def _noise_for(cfg, case, g, K, T, C):
@@ -159,17 +140,8 @@ def _noise_for(cfg, case, g, K, T, C):
 
 
 def _assert_parity(eng, orc, ctl, tag):
-    costs = eng.getSampledCostSeq()
-    assert np.isfinite(costs).all(), tag
-    dc = int(ulp_diff(costs, orc.costs()).max())
-    print("%s: costs %d ulp" % (tag, dc))
-    assert dc == 0, "%s: sampled costs differ from the oracle by up to %d ulp" % (tag, dc)
-    du = float(np.abs(eng.getControlSeq() - orc.control()).max())
-    print("%s: u* %g" % (tag, du))
-    assert du <= U_TOL, "%s: u* differs from the oracle by %g" % (tag, du)
-    if ctl in ("tube", "robust"):
-        dn = float(np.abs(eng.getNominalControlSeq() - orc.nominal_control()).max())
-        assert dn <= U_TOL, "%s: nominal u* differs from the oracle by %g" % (tag, dn)
+    du = check_against_oracle(dict(controller=ctl), eng, orc, tag, show=True)
+    assert du <= U_TOL, "%s: u* (or the nominal u*) differs from the oracle by %g" % (tag, du)
 
 
 def _run_parity(case, K, T):
@@ -178,13 +150,12 @@ def _run_parity(case, K, T):
     if ctl == "robust" and K < 3:
         with pytest.raises(m.MPPIError) as e:  # RobustMPPIController needs at least 3 candidates x 1 sample
             _make(case, K, T)
-        assert e.value.status == MPPI_ERR_INVALID_ARG, tag0
+        assert e.value.status == m.MPPI_ERR_INVALID_ARG, tag0
         return
     cfg, eng, orc, rob = _make(case, K, T)
     try:
         assert eng.sampler == NLN
-        C, S = eng.CONTROL_DIM, eng.STATE_DIM
-        x = cfg["x0"]
+        C = eng.CONTROL_DIM
         eng.setReductionMode(m.MPPI_REDUCTION_REFERENCE_ORDER)
         if case["independent"]:
             eng.setIndependentNoise(True)
@@ -193,29 +164,18 @@ def _run_parity(case, K, T):
         gen = 0  # the engine's generation counter: one per rollout launch, one per Robust candidate evaluation
         for call in range(2):
             tag = "%s call %d" % (tag0, call)
+            candidate_noise = None
             if ctl == "robust":
-                eps_is = None
                 if call > 0:  # (the first cycle has no nominal state yet and evaluates no candidates)
-                    eps_is = _noise_for(cfg, case, gen, K, T, C)
+                    candidate_noise = _noise_for(cfg, case, gen, K, T, C)
                     gen += 1
-                eng.updateImportanceSamplingControl(x, 1)
-                rob.update_importance_sampling(x, 1, eps_is)
-                if call == 0:
-                    g = np.random.default_rng(5).uniform(-0.3, 0.3, (T, S, C)).astype(np.float32)
-                    eng.setFeedbackGains(g)
-                    rob.set_gains(g)
             elif call > 0:
                 eng.slideControlSequence(1)
                 (orc.tube_slide if ctl == "tube" else orc.vanilla_slide)(1)
             eps = _noise_for(cfg, case, gen, K, T, C)[None]
             gen += 1
-            eng.computeControl(x, 1)
-            if ctl == "robust":
-                rob.compute_control(x, 1, eps)
-            elif ctl == "tube":
-                orc.tube_compute_control(x, 1, eps)
-            else:
-                orc.vanilla_compute_control(x, 1, eps)
+            # (the generator was seeded once, before the first call: no seed here)
+            compute_once(case, [eng], orc, rob, cfg, 1, eps, True, None, candidate_noise=candidate_noise, first_cycle=call == 0)
             info = eng.getLaunchInfo()
             got = {k: info[k] for k in ("family", "block", "rows_in_hbm")}
             assert got == case["expect"], "%s: launched %s, the case expects %s" % (tag, got, case["expect"])
@@ -353,16 +313,16 @@ def test_nln_moments_of_the_dumped_samples(gpu, kw):
 def test_nln_refusals(gpu):
     with pytest.raises(m.MPPIError) as e:
         m.VanillaMPPIController("cartpole", 128, 8, 0.02, 1.0, sampler=NLN, noise_source=MPPI_NOISE_ROCRAND_HOST)
-    assert e.value.status == MPPI_ERR_UNSUPPORTED and "NLN" in str(e.value), (e.value.status, str(e.value))
+    assert e.value.status == m.MPPI_ERR_UNSUPPORTED and "NLN" in str(e.value), (e.value.status, str(e.value))
     with pytest.raises(m.MPPIError) as e:
         m.ColoredMPPIController("cartpole", 128, 8, 0.02, 1.0, sampler=NLN)
-    assert e.value.status == MPPI_ERR_INVALID_ARG, e.value.status
+    assert e.value.status == m.MPPI_ERR_INVALID_ARG, e.value.status
     with pytest.raises(m.MPPIError) as e:
         m.VanillaMPPIController("cartpole", 128, 8, 0.02, 1.0, sampler=m.MPPI_SAMPLER_COLORED)
-    assert e.value.status == MPPI_ERR_INVALID_ARG, e.value.status
+    assert e.value.status == m.MPPI_ERR_INVALID_ARG, e.value.status
     with pytest.raises(m.MPPIError) as e:
         m.VanillaMPPIController("racer_dubins", 128, 8, 0.02, 1.0, sampler=NLN)
-    assert e.value.status == MPPI_ERR_UNKNOWN_MODEL, e.value.status
+    assert e.value.status == m.MPPI_ERR_UNKNOWN_MODEL, e.value.status
     # an NLN handle is no colored-noise handle; the Gaussian setters work on it
     eng = m.VanillaMPPIController("cartpole", 128, 8, 0.02, 1.0, sampler=NLN)
     try:
@@ -392,7 +352,7 @@ def test_nln_draw_uses_the_global_rollout_index_when_k_is_sharded(gpu, case):
     ranks, orc, cfg = [], None, None
     try:
         for r in range(W):
-            cfg, eng, o, _ = _make(case, K, T, rank=r, world_size=W)
+            cfg, eng, o, _ = _make(dict(case, kw=dict(case["kw"], rank=r, world_size=W)), K, T)
             ranks.append(eng)
             orc = orc or o
         x0 = cfg["x0"][None]

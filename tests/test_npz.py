@@ -82,7 +82,7 @@ def test_load_npz_autorally_equals_blob_path(gpu, tmp_path):
     assert ulp_diff(eng.rolloutCosts(cfg["x0"], 1), want).max() == 0
     with pytest.raises(m.MPPIError) as e:
         eng.loadNpz("dynamics", tmp_path / "track.npz")
-    assert e.value.status == 1 and "dynamics_W1" in str(e.value)
+    assert e.value.status == m.MPPI_ERR_INVALID_ARG and "dynamics_W1" in str(e.value)
     with pytest.raises(m.MPPIError):
         eng.loadNpz("lstm", tmp_path / "net.npz")
 
@@ -118,7 +118,7 @@ def test_load_npz_three_networks_of_the_racer_uncertainty_model(gpu, tmp_path, s
     terra/mean_network/, terra/uncertainty_network/; racer_dubins_elevation_lstm_unc.cu:30-33) through mppi_load_npz kinds
     "lstm" / "mean_lstm" / "unc_lstm" == the same networks through the blob path.  The loader sizes the networks from the
     archive as the reference does; other shapes than the reference's test shapes run one lane per rollout"""
-    from test_racer_dubins_lstm_unc import uncertainty_cfg
+    from racer_cfgs import uncertainty_cfg
     (hs, ms), (hm, mm), (hu, mu) = sizes
     nets = {"steering/model/": lstm_npz(seed=1, scale=0.06, I=4, H=hs, M=ms, OUT=1),
             "terra/mean_network/": lstm_npz(seed=2, scale=0.06, I=12, H=hm, M=mm, OUT=2),

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import mppi_generic_amd as m
-from common import cartpole_cfg, di_cfg, make_engine, make_oracle
+from common import cartpole_cfg, colored_cartpole, di_cfg, make_engine, make_oracle
 import pyoracle as po
 
 pytestmark = pytest.mark.gpu
@@ -66,9 +66,8 @@ def test_p2p_tsallis_weights_on_sharded_handles(gpu, world):
     exchanges per iteration, engine_iteration.hip: iterationShardedTsallis) — against the un-sharded engine on the same noise and
     against the oracle's un-sharded iteration"""
     from common import host_spectrum
-    from test_colored_noise import _colored_cartpole
     import gc
-    cfg = _colored_cartpole(K=2048, T=60)
+    cfg = colored_cartpole(K=2048, T=60)
     K, T = cfg["K"], cfg["T"]
     exps, decay, fmin = cfg["colored"]
     kw = dict(gamma=400.0, r_exp=1.7)
@@ -153,7 +152,7 @@ def test_p2p_missing_peer_times_out_instead_of_hanging(gpu):
         ranks[0].getStats()
     for c in ranks:
         c.close()
-    assert e.value.status == 9
+    assert e.value.status == m.MPPI_ERR_COMM
 
 
 def _ipc_worker(rank, world, conn, repo):

@@ -273,7 +273,7 @@ def test_buffered_plant_closed_loop_lstm_steering(gpu):
     every cycle once a second of history exists; what it set is initializeLSTM of exactly that history; and the engine's
     rollouts really start from it — an oracle whose blob carries the same (h0, c0) gives the same trajectory costs, 0 ulp."""
     from common import host_noise, make_oracle, ulp_diff
-    from test_racer_dubins_lstm_steering import H, LSTM_PARAMS, OUT_LAYERS, S_STEER, S_STEER_RATE, S_VEL, steering_cfg
+    from racer_cfgs import ELEVATION_S_STEER_RATE as S_STEER_RATE, H, LSTM_PARAMS, OUT_LAYERS, S_STEER, S_VEL, steering_cfg
     cfg = steering_cfg(K=1024, T=64)
     eng = make_engine(cfg)
     rng = np.random.default_rng(4)

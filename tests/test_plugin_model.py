@@ -50,7 +50,7 @@ def build_plugin(src=SRC, out=PLUGIN):
 @pytest.fixture(scope="module")
 def plugin():
     lib = m.load_library()
-    assert lib.mppi_load_plugin(build_plugin().encode()) == 0, lib.mppi_last_error(None)
+    assert lib.mppi_load_plugin(build_plugin().encode()) == m.MPPI_OK, lib.mppi_last_error(None)
     return lib
 
 
@@ -64,11 +64,11 @@ def test_plugin_builds_alone_and_registers(plugin):
 
 def test_register_model_argument_checks(plugin):
     fn = C.cast(plugin.mppi_device_count, C.c_void_p)  # any non-null function pointer
-    assert plugin.mppi_register_model(None, 0, fn, 0) == 1
-    assert plugin.mppi_register_model(b"x", 7, fn, 0) == 1
-    assert plugin.mppi_register_model(b"x", 0, fn, 12345) == 1  # header / library skew: the ABI fingerprint differs
+    assert plugin.mppi_register_model(None, 0, fn, 0) == m.MPPI_ERR_INVALID_ARG
+    assert plugin.mppi_register_model(b"x", 7, fn, 0) == m.MPPI_ERR_INVALID_ARG
+    assert plugin.mppi_register_model(b"x", 0, fn, 12345) == m.MPPI_ERR_INVALID_ARG  # header / library skew: the ABI fingerprint differs
     assert b"different mppi_amd/engine/model_instance.hpp" in plugin.mppi_last_error(None)
-    assert plugin.mppi_load_plugin(b"/nonexistent/libnothing.so") == 1
+    assert plugin.mppi_load_plugin(b"/nonexistent/libnothing.so") == m.MPPI_ERR_INVALID_ARG
 
 
 def test_barrier_bearing_model_forced_onto_the_pipeline_is_refused_at_registration(plugin):
@@ -86,9 +86,9 @@ def test_barrier_bearing_model_forced_onto_the_pipeline_is_refused_at_registrati
     assert "user_pendulum_forced_pipeline" not in plugin.mppi_list_models().decode().split("\n")
     # the C entry itself: ROLE_SEPARATED without BARRIER_FREE_DECLARED is refused, with it or without ROLE_SEPARATED it is not
     fn = C.cast(plugin.mppi_device_count, C.c_void_p)
-    assert plugin.mppi_register_model_checked(b"probe_forced", 0, fn, 0, 1) == 1
+    assert plugin.mppi_register_model_checked(b"probe_forced", 0, fn, 0, 1) == m.MPPI_ERR_INVALID_ARG
     assert b"MPPI_BARRIER_FREE_STEP" in plugin.mppi_last_error(None)
-    assert plugin.mppi_register_model_checked(b"probe_forced", 0, fn, 12345, 3) == 1  # passes the flag check, fails the fingerprint
+    assert plugin.mppi_register_model_checked(b"probe_forced", 0, fn, 12345, 3) == m.MPPI_ERR_INVALID_ARG  # passes the flag check, fails the fingerprint
     assert b"different mppi_amd/engine/model_instance.hpp" in plugin.mppi_last_error(None)
 
 
@@ -103,7 +103,7 @@ def test_barrier_bearing_pipeline_model_registered_unchecked_is_refused_at_creat
     assert "user_pendulum_forced_pipeline_unchecked" in plugin.mppi_list_models().decode().split("\n")
     with pytest.raises(m.MPPIError) as e:
         m.VanillaMPPIController("user_pendulum_forced_pipeline_unchecked", 256, 20, 0.02, 1.0)
-    assert e.value.status == 1 and "MPPI_BARRIER_FREE_STEP" in str(e.value) and "Dynamics" in str(e.value), str(e.value)
+    assert e.value.status == m.MPPI_ERR_INVALID_ARG and "MPPI_BARRIER_FREE_STEP" in str(e.value) and "Dynamics" in str(e.value), str(e.value)
 
 
 def test_in_tree_models_declare_barrier_free_steps_and_reference_style_ones_do_not():
@@ -204,7 +204,7 @@ def test_user_model_swings_up_in_closed_loop(gpu, plugin):
 # ------------------------------------------------------------------ a model file as a MPPI-Generic user has it ----------------
 @pytest.fixture(scope="module")
 def plugin_reference_style(plugin):
-    assert plugin.mppi_load_plugin(build_plugin(SRC_REF_STYLE, PLUGIN_REF_STYLE).encode()) == 0, plugin.mppi_last_error(None)
+    assert plugin.mppi_load_plugin(build_plugin(SRC_REF_STYLE, PLUGIN_REF_STYLE).encode()) == m.MPPI_OK, plugin.mppi_last_error(None)
     return plugin
 
 

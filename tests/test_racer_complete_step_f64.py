@@ -11,9 +11,9 @@ import math
 import numpy as np
 
 from common import make_oracle
-from test_racer_dubins_lstm_unc import (S_BRAKE, S_CGVZ, S_CGZ, S_OMEGA, S_PITCH, S_PITCH_RATE, S_ROLL, S_ROLL_RATE, S_STATIC_PITCH,
-                                        S_STATIC_ROLL, S_STEER, S_STEER_RATE, S_VEL, S_X, S_Y, S_YAW, UNC, NS, st, uncertainty_cfg)
-from test_racer_dubins_suspension import O_F_FWD, O_F_SIDE, O_F_UP, O_POS_Z, WHEELS, suspension_f64
+from racer_cfgs import (S_BRAKE, S_CGVZ, S_CGZ, S_OMEGA, S_PITCH, S_PITCH_RATE, S_ROLL, S_ROLL_RATE, S_STATIC_PITCH,
+                        S_STATIC_ROLL, S_STEER, S_STEER_RATE, S_VEL, S_X, S_Y, S_YAW, UNC, NS_UNCERTAINTY as NS,
+                        st26 as st, uncertainty_cfg, O_F_FWD, O_F_SIDE, O_F_UP, O_POS_Z, WHEELS, suspension_f64)
 
 PI = math.pi
 
@@ -220,8 +220,7 @@ def test_oracle_whole_step_against_float64():
 
 def test_oracle_suspension_whole_step_against_float64():
     """the parent class, RacerDubinsElevationSuspension (24 states), the same way — also listed as unpinned in DESIGN.md"""
-    from test_racer_dubins_suspension import suspension_cfg
-    from test_racer_dubins_suspension import st as st24
+    from racer_cfgs import suspension_cfg, st24
     rng = np.random.default_rng(78)
     sx, sy = -0.04, 0.06
     centres = (np.arange(240) + 0.5) * 0.25 - 30.0

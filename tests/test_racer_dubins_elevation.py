@@ -17,6 +17,7 @@ import pytest
 
 import pyoracle as po
 from common import host_noise, m, make_engine, make_oracle, ulp_diff
+from racer_cfgs import elevation_cfg, st  # bench.py imports elevation_cfg from this module
 
 YAW = math.pi / 6
 STEER = math.pi / 8
@@ -43,12 +44,6 @@ def test_step_params(gear_sign=1):
 
 
 test_step_params.__test__ = False
-
-
-def st(*v):
-    x = np.zeros(19, np.float32)
-    x[:len(v)] = v
-    return x
 
 
 G = 9.81
@@ -214,48 +209,6 @@ def test_oracle_static_settling_on_a_plane():
     o.set_blob("elevation_map", cliff)
     xn, xd, y = o.model_step_full(st(0.0, 0.0, 0.0, 0.0), np.zeros(2, np.float32), 0.02)
     assert abs(xn[S_PITCH] + math.asin(2.98 / 2.981)) <= 1e-4 and np.isfinite(xn).all()
-
-
-def hills(n=240, res=0.25):
-    """a smooth synthetic terrain, (blob, transform); world window [-30, 30]^2"""
-    c = (np.arange(n) + 0.5) * res - 30.0
-    X, Y = np.meshgrid(c, c)
-    z = 0.8 * np.sin(0.21 * X) * np.cos(0.17 * Y) + 0.03 * X + 0.4 * np.exp(-((X - 6) ** 2 + (Y - 3) ** 2) / 18.0)
-    transform = np.array([-30.0, -30.0, 0.0, 1, 0, 0, 0, 1, 0, 0, 0, 1, res, res, 1.0], np.float32)
-    return z.astype(np.float32), transform
-
-
-def elevation_cfg(K=1024, T=60, lambda_=0.5, num_iters=1, D=1, with_map=True):
-    """drive towards a way-point at 3 m/s over the hills, keeping the position variance small; outputs the model does not
-    produce (NaN) carry coefficient 0"""
-    cost = m.QuadraticCostParams28()
-    coeffs, goal = [0.0] * 28, [0.0] * 28
-    coeffs[0], goal[0] = 20.0, 3.0   # BASELINK_VEL_B_X
-    coeffs[2], goal[2] = 1.0, 8.0    # BASELINK_POS_I_X
-    coeffs[3], goal[3] = 1.0, 3.0    # BASELINK_POS_I_Y
-    coeffs[6] = 30.0                 # ROLL
-    coeffs[7] = 10.0                 # PITCH
-    coeffs[9] = 0.05                 # STEER_ANGLE_RATE
-    coeffs[17] = coeffs[18] = 5.0    # UNCERTAINTY_POS_X / _Y
-    cost.s_coeffs[:] = coeffs
-    cost.s_goal[:] = goal
-    x0 = np.zeros(19, np.float32)
-    x0[:9] = [1.0, 0.2, -4.0, -2.0, 0.03, 0.0, 0.0, 0.0, 0.0]
-    x0[9:13] = [0.01, 0.01, 0.001, 0.02]
-    cfg = dict(model="racer_dubins_elevation", K=K, T=T, D=D, dt=0.05, lambda_=lambda_, alpha=0.0, num_iters=num_iters,
-               dyn=m.RacerDubinsElevationParams(), cost=cost, ranges=[-1.0, 1.0, -1.0, 1.0], std_dev=[0.4, 0.5],
-               control_cost_coeff=[0.0, 0.0], x0=x0)
-    b = cfg["dyn"].base   # a drivable car: 5 m/s^2 at full throttle, drag 1/s, brakes 5 m/s^2 per 0.25 of brake state
-    b.c_0 = 0.0
-    b.c_t[:] = [5.0, 5.0, 5.0]
-    b.c_v[:] = [1.0, 1.0, 1.0]
-    b.c_b[:] = [20.0, 20.0, 20.0]
-    b.wheel_base = 2.981
-    b.steer_angle_scale = -2.45
-    if with_map:
-        heights, transform = hills()
-        cfg["blobs"] = {"elevation_map": heights, "elevation_map_transform": transform}
-    return cfg
 
 
 def test_oracle_closed_loop_over_the_hills():

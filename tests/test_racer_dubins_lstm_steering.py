@@ -10,37 +10,16 @@ out) and every network file under resources/ is a git-LFS stub, so what pins it 
   * LSTMHelper itself: tests/test_lstm_helper.py (known answers of tests/nn_helpers/lstm_helper_test.cu);
   * LSTMLSTMHelper: initializeLSTMLSTMTest (tests/nn_helpers/lstm_lstm_helper_test.cu:161-180): all parameters 1, a buffer of
     ones -> hidden = cell = 101."""
-import math
-
 import numpy as np
 import pytest
 
 import pyoracle as po
 from common import host_noise, m, make_engine, make_oracle, ulp_diff
-from test_racer_dubins_elevation import elevation_cfg, hills, st
+from racer_cfgs import (H, LSTM_PARAMS, OUT_LAYERS, elevation_cfg, hills, st,
+                        steering_cfg)  # bench.py imports steering_cfg from this module
 
 S_VEL, S_YAW, S_X, S_Y, S_STEER, S_BRAKE, S_ROLL, S_PITCH, S_STEER_RATE = range(9)
 O_STEER, O_STEER_RATE = 8, 9
-H, I = 4, 4
-LSTM_PARAMS = 4 * H * H + 4 * H * I + 4 * H
-OUT_LAYERS = [8, 20, 1]
-OUT_PARAMS = 8 * 20 + 20 + 20 * 1 + 1
-
-
-def steering_blobs(seed=21, scale=0.4, zero=False):
-    rng = np.random.default_rng(seed)
-    lstm = np.zeros(LSTM_PARAMS + 2 * H, np.float32) if zero else rng.uniform(-scale, scale, LSTM_PARAMS + 2 * H).astype(np.float32)
-    out = np.zeros(OUT_PARAMS, np.float32) if zero else rng.uniform(-scale, scale, OUT_PARAMS).astype(np.float32)
-    return {"lstm_weights": lstm, "lstm_output_weights": out}
-
-
-def steering_cfg(zero=False, **kw):
-    cfg = elevation_cfg(**kw)
-    cfg["model"] = "racer_dubins_elevation_lstm_steering"
-    blobs = dict(cfg.get("blobs", {}))
-    blobs.update(steering_blobs(zero=zero))
-    cfg["blobs"] = blobs
-    return cfg
 
 
 def test_lstm_lstm_helper_reference_known_answer():

@@ -14,46 +14,8 @@ import pytest
 
 import pyoracle as po
 from common import host_noise, m, make_engine, make_oracle, ulp_diff
-from test_racer_dubins_lstm_steering import steering_blobs
-from test_racer_dubins_suspension import suspension_cfg
-
-(S_VEL, S_YAW, S_X, S_Y, S_STEER, S_BRAKE, S_ROLL, S_PITCH, S_CGZ, S_CGVZ, S_ROLL_RATE, S_PITCH_RATE, S_STEER_RATE, S_OMEGA,
- S_STATIC_ROLL, S_STATIC_PITCH) = range(16)
-UNC = 16   # UNCERTAINTY_POS_X, _POS_Y, _YAW, _VEL_X, _POS_X_Y, _POS_X_YAW, _POS_X_VEL_X, _POS_Y_YAW, _POS_Y_VEL_X, _YAW_VEL_X
-NS = 26
-MEAN_LSTM, MEAN_OUT = 4 * 16 + 4 * 4 * 12 + 16 + 8, 20 * 16 + 20 + 2 * 20 + 2
-UNC_LSTM, UNC_OUT = 4 * 16 + 4 * 4 * 13 + 16 + 8, 20 * 17 + 20 + 5 * 20 + 5
-
-
-def st(*v):
-    x = np.zeros(NS, np.float32)
-    x[:len(v)] = v
-    return x
-
-
-def network_blobs(seed=33, scale=0.06, zero=False):
-    rng = np.random.default_rng(seed)
-    mk = (lambda n: np.zeros(n, np.float32)) if zero else (lambda n: rng.uniform(-scale, scale, n).astype(np.float32))
-    return {"mean_lstm_weights": mk(MEAN_LSTM), "mean_lstm_output_weights": mk(MEAN_OUT), "unc_lstm_weights": mk(UNC_LSTM),
-            "unc_lstm_output_weights": mk(UNC_OUT)}
-
-
-def uncertainty_cfg(zero=False, **kw):
-    cfg = suspension_cfg(zero_net=zero, **kw)
-    cfg["model"] = "racer_dubins_elevation_lstm_unc"
-    dyn = m.RacerDubinsUncertaintyParams()
-    src = cfg["dyn"]
-    C_bytes = bytes(src)
-    import ctypes as C
-    C.memmove(C.addressof(dyn.suspension), C_bytes, len(C_bytes))
-    dyn.unc_scale[:] = [1e-3] * 7   # the networks are random: keep their process noise from dominating the cost
-    cfg["dyn"] = dyn
-    x0 = np.zeros(NS, np.float32)
-    x0[:13] = cfg["x0"][:13]
-    x0[UNC:UNC + 4] = [0.01, 0.01, 0.001, 0.02]
-    cfg["x0"] = x0
-    cfg["blobs"].update(network_blobs(zero=zero))
-    return cfg
+from racer_cfgs import (S_BRAKE, S_OMEGA, S_PITCH, S_ROLL, S_STATIC_PITCH, S_STATIC_ROLL, S_VEL, S_YAW, UNC,
+                        st26 as st, suspension_cfg, uncertainty_cfg)  # bench.py imports uncertainty_cfg from this module
 
 
 def test_oracle_silent_networks_leave_the_suspension_model():

@@ -14,100 +14,8 @@ import pytest
 
 import pyoracle as po
 from common import host_noise, m, make_engine, make_oracle, ulp_diff
-from test_racer_dubins_elevation import hills
-from test_racer_dubins_lstm_steering import steering_blobs
-
-(S_VEL, S_YAW, S_X, S_Y, S_STEER, S_BRAKE, S_ROLL, S_PITCH, S_CGZ, S_CGVZ, S_ROLL_RATE, S_PITCH_RATE, S_STEER_RATE) = range(13)
-O_POS_Z, O_F_UP, O_F_FWD, O_F_SIDE = 4, 10, 11, 12
-NS = 24
-WHEELS = [(2.981, 0.737), (2.981, -0.737), (0.0, -0.737), (0.0, 0.737)]   # FL, FR, BL, BR as the reference places them
-
-
-def st(*v):
-    x = np.zeros(NS, np.float32)
-    x[:len(v)] = v
-    return x
-
-
-def normals_of(z, res):
-    """unit normals of a height field z[row = y][col = x] sampled every `res` metres: {h, w, 4}"""
-    dzdy, dzdx = np.gradient(z.astype(np.float64), res)
-    n = np.stack([-dzdx, -dzdy, np.ones_like(dzdx), np.zeros_like(dzdx)], axis=-1)
-    n[..., :3] /= np.linalg.norm(n[..., :3], axis=-1, keepdims=True)
-    return n.astype(np.float32)
-
-
-def suspension_cfg(K=1024, T=60, lambda_=0.5, D=1, maps="both", zero_net=False):
-    cost = m.QuadraticCostParams28()
-    coeffs, goal = [0.0] * 28, [0.0] * 28
-    coeffs[0], goal[0] = 20.0, 3.0   # BASELINK_VEL_B_X
-    coeffs[2], goal[2] = 1.0, 8.0    # BASELINK_POS_I_X
-    coeffs[3], goal[3] = 1.0, 3.0    # BASELINK_POS_I_Y
-    coeffs[6] = 30.0                 # ROLL
-    coeffs[7] = 10.0                 # PITCH
-    coeffs[9] = 0.05                 # STEER_ANGLE_RATE
-    coeffs[10] = 1e-7                # WHEEL_FORCE_UP_MAX
-    coeffs[12] = 1e-7                # WHEEL_FORCE_SIDE_MAX
-    coeffs[17] = coeffs[18] = 5.0    # UNCERTAINTY_POS_X / _Y
-    cost.s_coeffs[:] = coeffs
-    cost.s_goal[:] = goal
-    dyn = m.RacerDubinsSuspensionParams()
-    b = dyn.base
-    b.c_0 = 0.0
-    b.c_t[:] = [5.0, 5.0, 5.0]
-    b.c_v[:] = [1.0, 1.0, 1.0]
-    b.c_b[:] = [20.0, 20.0, 20.0]
-    b.wheel_base = 2.981
-    b.steer_angle_scale = -2.45
-    x0 = np.zeros(NS, np.float32)
-    x0[:8] = [1.0, 0.2, -4.0, -2.0, 0.03, 0.0, 0.0, 0.0]
-    x0[13:17] = [0.01, 0.01, 0.001, 0.02]
-    blobs = {}
-    if maps in ("both", "elevation"):
-        z, transform = hills()
-        blobs["elevation_map"] = z
-        blobs["elevation_map_transform"] = transform
-        if maps == "both":
-            blobs["normals_map"] = normals_of(z, 0.25)
-        # the centre of gravity starts one wheel radius above the terrain under the car
-        col, row = int((x0[S_X] + 1.49 + 30.0) / 0.25), int((x0[S_Y] + 30.0) / 0.25)
-        x0[S_CGZ] = z[row, col] + 0.32
-    else:
-        x0[S_CGZ] = 0.32
-    blobs.update(steering_blobs(zero=zero_net))
-    return dict(model="racer_dubins_elevation_suspension", K=K, T=T, D=D, dt=0.02, lambda_=lambda_, alpha=0.0, num_iters=1,
-                dyn=dyn, cost=cost, ranges=[-1.0, 1.0, -1.0, 1.0], std_dev=[0.4, 0.5], control_cost_coeff=[0.0, 0.0], x0=x0,
-                blobs=blobs)
-
-
-def suspension_f64(p, x, height_of, normal_of):
-    """float64 restatement of computeSimpleSuspensionStep (…suspension_lstm.cu:199-340): (acc_z, acc_roll, acc_pitch, up_max,
-    fwd_max, side_max)"""
-    roll, pitch, yaw = float(x[S_ROLL]), float(x[S_PITCH]), float(x[S_YAW])
-    cr, sr, cp, sp_, cy, sy = math.cos(roll), math.sin(roll), math.cos(pitch), math.sin(pitch), math.cos(yaw), math.sin(yaw)
-    M = np.array([[cp * cy, sr * sp_ * cy - cr * sy, cr * sp_ * cy + sr * sy],
-                  [cp * sy, sr * sp_ * sy + cr * cy, cr * sp_ * sy - sr * cy],
-                  [-sp_, sr * cp, cr * cp]])
-    az = aroll = apitch = 0.0
-    up, fwd, side = [], [], []
-    for i, (bx, by) in enumerate(WHEELS):
-        wyaw = yaw + (4 / -9.1 if i < 2 else 0.0)
-        c, s = math.cos(wyaw), math.sin(wyaw)
-        world = M @ np.array([bx, by, 0.0]) + np.array([float(x[S_X]), float(x[S_Y]), 0.0])
-        h = height_of(world)
-        n = normal_of(world)
-        cgx, cgy = bx - p.c_g[0], by - p.c_g[1]
-        pos_z = float(x[S_CGZ]) + roll * cgy - pitch * cgx - p.wheel_radius
-        vel_z = float(x[S_CGVZ]) + float(x[S_ROLL_RATE]) * cgy - float(x[S_PITCH_RATE]) * cgx
-        h_dot = -(float(x[S_VEL]) * c * n[0] + float(x[S_VEL]) * s * n[1])
-        f = -p.spring_k * (pos_z - h) - p.drag_c * (vel_z - h_dot)
-        up.append(f)
-        fwd.append(abs(f / n[2] * (n[0] * c + n[1] * s + n[2] * -pitch)))
-        side.append(abs(f / n[2] * (-n[0] * s + n[1] * c + n[2] * roll)))
-        az += f / p.mass
-        aroll += f * cgy / p.I_xx
-        apitch += -f * cgx / p.I_yy
-    return az, aroll, apitch, max(up), max(fwd), max(side)
+from racer_cfgs import (O_F_FWD, O_F_SIDE, O_F_UP, O_POS_Z, S_CGVZ, S_CGZ, S_PITCH, S_PITCH_RATE, S_ROLL, S_ROLL_RATE, S_VEL,
+                        S_X, S_Y, hills, st24 as st, suspension_cfg, suspension_f64)  # bench.py imports suspension_cfg from this module
 
 
 def test_oracle_rest_on_flat_ground_is_an_equilibrium():

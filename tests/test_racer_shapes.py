@@ -5,10 +5,7 @@ import numpy as np
 import pytest
 
 from common import host_noise, make_engine, make_oracle, ulp_diff
-from test_racer_dubins_elevation import elevation_cfg
-from test_racer_dubins_lstm_steering import steering_cfg
-from test_racer_dubins_lstm_unc import uncertainty_cfg
-from test_racer_dubins_suspension import suspension_cfg
+from racer_cfgs import elevation_cfg, steering_cfg, uncertainty_cfg, suspension_cfg
 
 MODELS = {"elevation": elevation_cfg, "lstm_steering": steering_cfg, "suspension": suspension_cfg, "complete": uncertainty_cfg}
 CASES = [  # K, T, systems, lanes per rollout, kernel variant (0 auto, 1 fused, 2 role-pipelined)

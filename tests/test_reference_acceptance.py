@@ -33,12 +33,9 @@ import pytest
 import mppi_generic_amd as m
 import pyoracle as po
 from common import make_engine, make_oracle
+from restate64 import bits
 
 DT_DI = np.float32(0.02)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def ddp_gains_linear(T, dt, Q, Qf, R):
@@ -325,7 +322,7 @@ def _compare_traces(a, b, what):
     assert len(a) == len(b), (what, len(a), len(b))
     for i, (ra, rb) in enumerate(zip(a, b)):
         for j, (va, vb) in enumerate(zip(ra, rb)):
-            assert np.array_equal(_bits(va), _bits(vb)), "%s: step %d, item %d: %r != %r" % (what, i, j, va, vb)
+            assert np.array_equal(bits(va), bits(vb)), "%s: step %d, item %d: %r != %r" % (what, i, j, va, vb)
 
 
 @pytest.mark.gpu

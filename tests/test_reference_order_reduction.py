@@ -17,15 +17,11 @@ import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import autorally_cfg, cartpole_cfg, di_cfg, host_noise, make_engine, make_oracle, ulp_diff
+from common import U_TOL, autorally_cfg, cartpole_cfg, colored_cartpole, di_cfg, host_noise, make_engine, make_oracle, ulp_diff
+from restate64 import bits
 
 pytestmark = pytest.mark.gpu
 
-U_TOL = 1e-5
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("K,lam", [(10000, 0.5), (1000, 0.25), (16384, 20.0), (20000, 1.0), (37, 3.0)])
@@ -38,10 +34,10 @@ def test_weights_and_statistics_reference_order(gpu, K, lam):
     base = po.baseline(costs)
     w_o = po.norm_exp(costs, np.float32(1.0 / lam), base)
     assert st[0] == base
-    assert np.array_equal(_bits(w), _bits(w_o))
+    assert np.array_equal(bits(w), bits(w_o))
     assert st[1] == po.normalizer(w_o)
     fe = po.free_energy(w_o, base, lam)
-    assert np.array_equal(_bits(st[2:5]), _bits(fe)), (st[2:5], fe)
+    assert np.array_equal(bits(st[2:5]), bits(fe)), (st[2:5], fe)
 
 
 def test_weights_reference_order_sum_is_order_sensitive(gpu):
@@ -71,9 +67,9 @@ def test_weighted_reduction_reference_order(gpu, K, T, C, stride, fma):
     finally:
         po.set_reduction_fma(False)
     u_g = m.weighted_reduction_reference_order(w, v, eta, stride, fma)
-    assert np.array_equal(_bits(u_g), _bits(u_o))
+    assert np.array_equal(bits(u_g), bits(u_o))
     if not fma and K >= 1024 and stride > 1:  # the two flavours are different functions (otherwise the parametrisation tests nothing)
-        assert not np.array_equal(_bits(u_g), _bits(m.weighted_reduction_reference_order(w, v, eta, stride, True)))
+        assert not np.array_equal(bits(u_g), bits(m.weighted_reduction_reference_order(w, v, eta, stride, True)))
 
 
 @pytest.mark.parametrize("variant", [m.MPPI_KERNEL_PIPELINE, m.MPPI_KERNEL_FUSED], ids=["pipeline", "fused"])
@@ -93,8 +89,8 @@ def test_iterations_bit_identical(gpu, variant, soft):
     st, so = eng.getStats().real_sys, orc.stats()
     assert st.baseline == so["baseline"][0] and st.normalizer == so["normalizer"][0]
     assert st.free_energy_mean == so["free_energy"][0] and st.free_energy_variance == so["free_energy_var"][0]
-    assert np.array_equal(_bits(eng.getControlSeq()), _bits(orc.control()))
-    assert np.array_equal(_bits(eng.getTargetStateSeq()), _bits(orc.state_traj()))
+    assert np.array_equal(bits(eng.getControlSeq()), bits(orc.control()))
+    assert np.array_equal(bits(eng.getTargetStateSeq()), bits(orc.state_traj()))
     eng.close()
 
 
@@ -111,7 +107,7 @@ def test_mode_switch_and_sum_strides(gpu):
     eng.setReductionMode(m.MPPI_REDUCTION_REFERENCE_ORDER)
     eng.updateImportanceSampler(np.zeros_like(u_fused))
     eng.computeControl(cfg["x0"], 1)
-    assert np.array_equal(_bits(eng.getControlSeq()), _bits(u_o32))
+    assert np.array_equal(bits(eng.getControlSeq()), bits(u_o32))
     assert np.abs(u_fused - u_o32).max() <= U_TOL
     # cells of 7 rollouts (ragged: 1000 = 142 * 7 + 6)
     eng.setSamplingParams(cfg["std_dev"], cfg["control_cost_coeff"], sum_strides=7)
@@ -120,7 +116,7 @@ def test_mode_switch_and_sum_strides(gpu):
     orc.vanilla_compute_control(cfg["x0"], 1, eps)
     eng.updateImportanceSampler(np.zeros_like(u_fused))
     eng.computeControl(cfg["x0"], 1)
-    assert np.array_equal(_bits(eng.getControlSeq()), _bits(orc.control()))
+    assert np.array_equal(bits(eng.getControlSeq()), bits(orc.control()))
     # fma flavour (nvcc's default contraction of `inter += weight * v`)
     eng.setReductionMode(m.MPPI_REDUCTION_REFERENCE_ORDER_FMA)
     po.set_reduction_fma(True)
@@ -131,20 +127,20 @@ def test_mode_switch_and_sum_strides(gpu):
         po.set_reduction_fma(False)
     eng.updateImportanceSampler(np.zeros_like(u_fused))
     eng.computeControl(cfg["x0"], 1)
-    assert np.array_equal(_bits(eng.getControlSeq()), _bits(orc.control()))
+    assert np.array_equal(bits(eng.getControlSeq()), bits(orc.control()))
     eng.setReductionMode(m.MPPI_REDUCTION_FUSED)
     eng.updateImportanceSampler(np.zeros_like(u_fused))
     eng.computeControl(cfg["x0"], 1)
-    assert np.array_equal(_bits(eng.getControlSeq()), _bits(u_fused))
+    assert np.array_equal(bits(eng.getControlSeq()), bits(u_fused))
     with pytest.raises(m.MPPIError) as e:
         eng.setReductionMode(7)
-    assert e.value.status == 1
+    assert e.value.status == m.MPPI_ERR_INVALID_ARG
     eng.close()
     # a K-sharded handle refuses: the reference order runs over ALL rollouts
     sh = m.VanillaMPPIController("cartpole", 1024, 20, 0.02, 1.0, rank=0, world_size=2)
     with pytest.raises(m.MPPIError) as e:
         sh.setReductionMode(m.MPPI_REDUCTION_REFERENCE_ORDER)
-    assert e.value.status == 10
+    assert e.value.status == m.MPPI_ERR_UNSUPPORTED
     sh.close()
 
 
@@ -153,8 +149,7 @@ def test_colored_mppi_reference_order(gpu, tsallis):
     """ColoredMPPI (colored-noise sampler; with and without Tsallis weights, core/mppi_common.cu:968-985) in the reference-order
     mode: four closed-loop steps, control sequence and state trajectory bit for bit"""
     from common import host_spectrum
-    from test_colored_noise import _colored_cartpole
-    cfg = _colored_cartpole(K=2048, T=60)
+    cfg = colored_cartpole(K=2048, T=60)
     eng, orc = make_engine(cfg), make_oracle(cfg)
     eng.setReductionMode(m.MPPI_REDUCTION_REFERENCE_ORDER)
     exps, decay, fmin = cfg["colored"]
@@ -167,8 +162,8 @@ def test_colored_mppi_reference_order(gpu, tsallis):
         eng.injectNoise(z)
         eng.computeControl(x, 1)
         orc.colored_compute_control(x, 1, z, exps, decay, fmin)
-        assert np.array_equal(_bits(eng.getControlSeq()), _bits(orc.control())), i
-        assert np.array_equal(_bits(eng.getTargetStateSeq()), _bits(orc.state_traj())), i
+        assert np.array_equal(bits(eng.getControlSeq()), bits(orc.control())), i
+        assert np.array_equal(bits(eng.getTargetStateSeq()), bits(orc.state_traj())), i
         st, so = eng.getStats().real_sys, orc.stats()
         assert st.baseline == so["baseline"][0] and st.normalizer == so["normalizer"][0], i
         x, _ = orc.model_step(x, orc.control()[0])
@@ -195,10 +190,10 @@ def test_tube_free_running_closed_loop_100_steps(gpu):
         orc.tube_compute_control(x_o, 1, eps)
         u_e, u_o = eng.getControlSeq(), orc.control()
         assert np.abs(u_e - u_o).max() <= U_TOL, i
-        assert np.array_equal(_bits(u_e), _bits(u_o)), i
-        assert np.array_equal(_bits(eng.getNominalControlSeq()), _bits(orc.nominal_control())), i
-        assert np.array_equal(_bits(eng.getTargetStateSeq()), _bits(orc.state_traj())), i
-        assert np.array_equal(_bits(eng.getNominalStateSeq()), _bits(orc.nominal_state_traj())), i
+        assert np.array_equal(bits(u_e), bits(u_o)), i
+        assert np.array_equal(bits(eng.getNominalControlSeq()), bits(orc.nominal_control())), i
+        assert np.array_equal(bits(eng.getTargetStateSeq()), bits(orc.state_traj())), i
+        assert np.array_equal(bits(eng.getNominalStateSeq()), bits(orc.nominal_state_traj())), i
         st, so = eng.getStats(), orc.stats()
         assert st.real_sys.baseline == so["baseline"][0] and st.nominal_sys.baseline == so["baseline"][1], i
         assert st.real_sys.normalizer == so["normalizer"][0] and st.nominal_sys.normalizer == so["normalizer"][1], i
@@ -210,7 +205,7 @@ def test_tube_free_running_closed_loop_100_steps(gpu):
             kick += np.array([0.8, -0.6, 0.5, 0.5], np.float32)
         x_e, _ = eng.modelStep(x_e, u_e[0])
         x_o, _ = orc.model_step(x_o, u_o[0])
-        assert np.array_equal(_bits(x_e), _bits(x_o)), i
+        assert np.array_equal(bits(x_e), bits(x_o)), i
         x_e, x_o = x_e + kick, x_o + kick
         eng.slideControlSequence(1)
         orc.tube_slide(1)
@@ -266,23 +261,23 @@ def test_robust_free_running_closed_loop(gpu, model, K, T, steps):
         ns_g, best_g, stride_g, fe_g = eng.getRMPPIState()
         ns_o, best_o, stride_o, fe_o = rob.state()
         assert best_g == best_o and stride_g == stride_o, i
-        assert np.array_equal(_bits(ns_g), _bits(ns_o)), i
+        assert np.array_equal(bits(ns_g), bits(ns_o)), i
         if not first:
-            assert np.array_equal(_bits(fe_g), _bits(fe_o)), i
+            assert np.array_equal(bits(fe_g), bits(fe_o)), i
             used.add(best_g)
         eng.computeControl(x_e, 1)
         rob.compute_control(x_o, 1, eps[1:])
         u_e, u_o = eng.getControlSeq(), orc.control()
         assert np.abs(u_e - u_o).max() <= U_TOL, i
-        assert np.array_equal(_bits(u_e), _bits(u_o)), i
-        assert np.array_equal(_bits(eng.getNominalControlSeq()), _bits(orc.nominal_control())), i
-        assert np.array_equal(_bits(eng.getTargetStateSeq()), _bits(orc.nominal_state_traj())), i
+        assert np.array_equal(bits(u_e), bits(u_o)), i
+        assert np.array_equal(bits(eng.getNominalControlSeq()), bits(orc.nominal_control())), i
+        assert np.array_equal(bits(eng.getTargetStateSeq()), bits(orc.nominal_state_traj())), i
         st, so = eng.getStats(), orc.stats()
         assert st.nominal_sys.baseline == so["baseline"][0] and st.real_sys.baseline == so["baseline"][1], i
         assert st.nominal_sys.normalizer == so["normalizer"][0] and st.real_sys.normalizer == so["normalizer"][1], i
         x_e, _ = eng.modelStep(x_e, u_e[0])
         x_o, _ = orc.model_step(x_o, u_o[0])
-        assert np.array_equal(_bits(x_e), _bits(x_o)), i
+        assert np.array_equal(bits(x_e), bits(x_o)), i
         kick = np.zeros(S, np.float32)
         kick[:4] = rng.normal(0, 0.02, 4)
         x_e, x_o = x_e + kick, x_o + kick

@@ -18,7 +18,7 @@ K, T = 256, 20
 
 def _live(lib):
     n, b = C.c_int64(), C.c_int64()
-    assert lib.mppi_debug_live_allocations(C.byref(n), C.byref(b)) == 0
+    assert lib.mppi_debug_live_allocations(C.byref(n), C.byref(b)) == m.MPPI_OK
     return n.value, b.value
 
 

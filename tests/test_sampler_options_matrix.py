@@ -52,11 +52,12 @@ import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import host_noise, host_spectrum, ulp_diff
-from test_kernel_matrix import BUILDERS, SOFTMIN_RTOL, U_TOL, _make, _registrations, build_cases
-from test_kernel_sequence import _ranges, constrain64, expects_streamed_merge, softmin64
+from common import PHILOX_SEED, U_TOL, host_noise, host_spectrum, make_oracle
+from kernel_forms import (BUILDERS, build_cases, check_against_oracle, check_form, compute_once, expects_streamed_merge,
+                          make_handles, registrations)
+from restate64 import (SOFTMIN_RTOL, bits_equal, constrain64, first_pure_rollout, likelihood_ratio64, likelihood_ratio_bound,
+                       ranges32, sample_rule64, softmin64)
 
-MPPI_ERR_UNSUPPORTED = 10
 SETS = ("table", "per-control")
 DECAY, ALPHA, PURE_PCT = 0.9, 0.1, 0.25
 COEFF = (0.7, 0.3)
@@ -69,8 +70,6 @@ KT_INJECTED = [(65, 3), (200, 5), (1049, 9)]
 KT_PHILOX = (65, 17)
 KT_TWO_ITERS = [(200, 5), (1049, 9)]
 KT_STREAMED = (200, 8)  # T C % 4 == 0 for one and two controls: the fused 64x1x1 pipeline streams its merge (Philox only)
-SEED = 77
-EPS32 = float(np.finfo(np.float32).eps)  # 2^-23
 
 # plugins whose enforceConstraints depends on the state: constrain64 cannot restate their clamp -> model name: reason.  No
 # registered plugin declares CONSTRAINTS_DEPEND_ON_STATE (test_coverage holds the list to those that do).
@@ -94,21 +93,8 @@ FUSED_DRIFT = {
 }
 
 
-def ranges32(cfg, C):
-    """the control ranges as the engine and the oracle hold them: rounded to fp32"""
-    lo, hi = _ranges(cfg, C)
-    return lo.astype(np.float32).astype(np.float64), hi.astype(np.float32).astype(np.float64)
-
-
 def stride_of(T):
     return 2 if T >= 5 else 1
-
-
-def first_pure_rollout(K, pct=PURE_PCT):
-    """the reference's compare (gaussian.cu:108): (float) k >= (1 - p) * (float) K in fp32 -> the first k that is pure noise"""
-    edge = (np.float32(1.0) - np.float32(pct)) * np.float32(K)
-    k = np.arange(K + 1)
-    return int(k[k.astype(np.float32) >= edge][0])
 
 
 @functools.lru_cache(maxsize=None)
@@ -172,14 +158,14 @@ class Options:
         K, T, C, D = self.K, self.T, self.C, self.D
         if self.controller == "colored":
             if philox:
-                return None, np.stack([po.philox_spectrum(SEED, g, K, T, C) for g in range(n_iters)])
+                return None, np.stack([po.philox_spectrum(PHILOX_SEED, g, K, T, C) for g in range(n_iters)])
             z = host_spectrum(n_iters, K, T, C, seed=K + T)
             return z, z
         if philox:
             if self.independent:
-                return None, np.stack([np.stack([po.philox_normal(SEED, g, K, T, C, stream=d) for d in range(D)])
+                return None, np.stack([np.stack([po.philox_normal(PHILOX_SEED, g, K, T, C, stream=d) for d in range(D)])
                                        for g in range(n_iters)])
-            return None, np.stack([po.philox_normal(SEED, g, K, T, C) for g in range(n_iters)])
+            return None, np.stack([po.philox_normal(PHILOX_SEED, g, K, T, C) for g in range(n_iters)])
         if self.independent:
             eps = np.random.Generator(np.random.Philox(K + T)).standard_normal((n_iters, D, K, T, C), dtype=np.float32)
         else:
@@ -194,44 +180,9 @@ class Options:
         return eps[0][z] if self.independent else eps[0]
 
 
-# ------------------------------------------------------------------ float64 restatements (numpy only) ------------------
-def sample_rule64(mean, sigma, eps, stride, first_pure, lo_hi, iteration=0, decay=DECAY):
-    """setGaussianControls (gaussian.cu:99-127) and the base clamp in float64.  mean [T][C], sigma [T][C] undecayed, eps
-    [K][T][C] -> (v [K][T][C], bound [K][T][C])"""
-    m = np.asarray(mean, np.float64)[None]
-    se = (decay ** iteration) * np.asarray(sigma, np.float64)[None] * np.asarray(eps, np.float64)
-    K, T, _ = se.shape
-    v = m + se
-    pure = np.arange(K) >= first_pure
-    v[pure] = se[pure]
-    use_mean = np.zeros((K, T), bool)
-    use_mean[0, :] = True
-    use_mean[:, :stride] = True
-    v[use_mean] = np.broadcast_to(m, v.shape)[use_mean]
-    bound = 2.0 ** -21 * np.maximum(1.0, np.abs(m) + np.abs(se))
-    lo, hi = lo_hi
-    return np.minimum(np.maximum(v, lo), hi), bound
-
-
-def likelihood_ratio64(v, mean, sigma, coeff, first_pure, lambda_, alpha):
-    """(1/T) sum_t LR_t and (1/T) sum_t |LR_t| per rollout, LR_t = 0.5 lambda (1 - alpha) sum_j c_j mu_j (mu_j - 2 v_j) / sigma_j^2
-    (gaussian.cu:480-569) with mu = 0 on pure-noise rollouts; v [K][T][C] clamped controls, mean / sigma [T][C]"""
-    v = np.asarray(v, np.float64)
-    K, T, _ = v.shape
-    mu = np.broadcast_to(np.asarray(mean, np.float64)[None], v.shape).copy()
-    mu[np.arange(K) >= first_pure] = 0.0
-    s = np.asarray(sigma, np.float64)[None]
-    lr = 0.5 * lambda_ * (1.0 - alpha) * (np.asarray(coeff, np.float64) * mu * (mu - 2.0 * v) / (s * s)).sum(2)
-    return lr.sum(1) / T, np.abs(lr).sum(1) / T
-
-
-def likelihood_ratio_bound(T, s_coeff, s_zero, lr_abs):
-    return (T + 4) * EPS32 * (np.maximum(np.abs(s_coeff), np.abs(s_zero)) + lr_abs)
-
-
 # ------------------------------------------------------------------ cases -----------------------------------------------
 def option_cases():
-    regs = {(n, s): d for n, s, d in _registrations()}
+    regs = {(n, s): d for n, s, d in registrations()}
     out = []
     for case in build_cases():
         if case["refuse"]:
@@ -246,14 +197,13 @@ def option_cases():
 CASES = option_cases()
 # as enumerated when this module is imported: tests that run earlier in a session may register models of their own
 # (plugins, templated examples), which are theirs to hold to the oracle
-REGISTRATIONS = _registrations()
+REGISTRATIONS = registrations()
 
 
 # ------------------------------------------------------------------ CPU ------------------------------------------------
 def _oracle_run(model, controller, set_name, K, T, zero_coeff=False):
     """the oracle alone, one iteration with injected noise: (options, cfg, costs [D][K], clamped samples [D][K][T][C], eps)"""
     opt = Options(model, controller, set_name, K, T, zero_coeff)
-    from common import make_oracle
     cfg = BUILDERS[model](K, T, opt.D)
     cfg["D"] = opt.D
     cfg["num_iters"] = 1
@@ -279,14 +229,14 @@ def test_likelihood_ratio_share_and_restatements(model, set_name):
         tag = "%s %s %s" % (model, controller, set_name)
         assert np.array_equal(v, v0), tag
         assert np.isfinite(s_coeff).all() and np.isfinite(s_zero).all(), tag
-        fp = first_pure_rollout(K)
+        fp = first_pure_rollout(K, PURE_PCT)
         assert float(np.abs(opt.mean[opt.stride:]).max()) > 0 and float(np.abs(opt.mean).min()) > 0, tag
         lo_hi = ranges32(cfg, opt.C)
         assert (opt.mean.astype(np.float64) > lo_hi[0]).all() and (opt.mean.astype(np.float64) < lo_hi[1]).all(), tag
         for z in range(opt.D):
             share = float(np.median(np.abs(s_coeff[z] - s_zero[z]) / np.abs(s_zero[z])))
             assert share >= 1e-3, "%s system %d: the likelihood-ratio term is %g of the cost (median)" % (tag, z, share)
-            want, bound = sample_rule64(opt.mean, opt.sigma[z], opt.eps_of_system(eps, z), opt.stride, fp, lo_hi)
+            want, bound = sample_rule64(opt.mean, opt.sigma[z], opt.eps_of_system(eps, z), opt.stride, fp, lo_hi, DECAY)
             err = np.abs(v[z].astype(np.float64) - want)
             assert (err <= bound).all(), "%s system %d: sample rule off by %g" % (tag, z, float((err - bound).max()))
             if model not in SAMPLE_RULE_SKIP:
@@ -318,8 +268,8 @@ def test_option_sets_differ_where_a_wrong_source_must_show():
 
 def test_pure_noise_boundaries():
     """(1 - 0.25) K in fp32: 48.75, 150.0 (the equality edge: rollout 150 is pure) and 786.75 — against the oracle's isPureNoise"""
-    assert [first_pure_rollout(K) for K, _ in KT_INJECTED] == [49, 150, 787]
-    assert first_pure_rollout(KT_PHILOX[0]) == 49
+    assert [first_pure_rollout(K, PURE_PCT) for K, _ in KT_INJECTED] == [49, 150, 787]
+    assert first_pure_rollout(KT_PHILOX[0], PURE_PCT) == 49
     assert np.float32(PURE_PCT) == PURE_PCT and (np.float32(1) - np.float32(PURE_PCT)) * np.float32(200) == np.float32(150)
     for K, T in KT_INJECTED:
         orc = po.Oracle("cartpole", K, T, 1)
@@ -327,7 +277,7 @@ def test_pure_noise_boundaries():
         v = orc.set_gaussian_controls(np.ones((1, T, 1), np.float32), np.zeros((K, T, 1), np.float32), 0, 0)
         # zero noise around a mean of one: a rollout that uses the mean holds 1, a pure-noise rollout 0; rollout 0 is the mean
         pure = v[0, :, T - 1, 0] == 0
-        fp = first_pure_rollout(K)
+        fp = first_pure_rollout(K, PURE_PCT)
         assert not pure[:fp].any() and pure[fp:].all(), (K, fp)
 
 
@@ -356,63 +306,11 @@ def test_coverage():
 
 
 # ------------------------------------------------------------------ GPU ------------------------------------------------
-def _bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and bool(np.all(a.view(np.uint32) == b.view(np.uint32)))
-
-
 def _compute(case, opt, cfg, engines, orc, rob, philox, n_iters):
     """one computeControl of n_iters iterations on every engine and on the oracle, from the same noise; returns that noise"""
-    ctl = case["controller"]
-    inject, eps = opt.noise(n_iters, philox)
-    x0 = cfg["x0"]
-    for e in engines:
-        if philox:
-            e.setSeed(SEED)
-        else:
-            e.injectNoise(inject)
-    if ctl == "robust":
-        gains = np.random.default_rng(5).uniform(-0.3, 0.3, (opt.T, engines[0].STATE_DIM, opt.C)).astype(np.float32)
-        # first cycle: no nominal state yet, no candidates, no noise drawn (robust_mppi_controller.cu:508-633)
-        for e in engines:
-            e.updateImportanceSamplingControl(x0, opt.stride)
-            e.setFeedbackGains(gains)
-        rob.update_importance_sampling(x0, opt.stride, None)
-        rob.set_gains(gains)
-    for e in engines:
-        e.computeControl(x0, opt.stride)
-    if ctl == "colored":
-        orc.colored_compute_control(x0, opt.stride, eps, *cfg["colored"])
-    elif ctl == "robust":
-        rob.compute_control(x0, opt.stride, eps)
-    elif ctl == "tube":
-        orc.tube_compute_control(x0, opt.stride, eps)
-    else:
-        orc.vanilla_compute_control(x0, opt.stride, eps)
+    _, eps = opt.noise(n_iters, philox)
+    compute_once(case, engines, orc, rob, cfg, opt.stride, eps, philox, PHILOX_SEED)
     return eps
-
-
-def _check_form(case, eng, tag, streamed=False):
-    info = eng.getLaunchInfo()
-    got = {k: info[k] for k in ("family", "block", "rows_in_hbm")}
-    assert got == case["expect"], "%s: launched %s, the case expects %s" % (tag, got, case["expect"])
-    assert info["streamed_merge"] == streamed, "%s: streamed_merge %s, expected %s" % (tag, info["streamed_merge"], streamed)
-
-
-def _check_against_oracle(case, eng, orc, tag, costs_exact=True):
-    """costs (and samples) 0 ulp where the handle reduces as the oracle does, u* and the nominal u* within 1e-5 -> the
-    largest control difference"""
-    costs = eng.getSampledCostSeq()
-    assert np.isfinite(costs).all(), tag
-    if costs_exact:
-        dc = int(ulp_diff(costs, orc.costs()).max())
-        assert dc == 0, "%s: sampled costs differ from the oracle by up to %d ulp" % (tag, dc)
-        dv = int(ulp_diff(eng.getSampledControls(), orc.samples()).max())
-        assert dv == 0, "%s: dumped samples differ from the oracle's clamped samples by up to %d ulp" % (tag, dv)
-    du = float(np.abs(eng.getControlSeq() - orc.control()).max())
-    if case["controller"] in ("tube", "robust"):
-        du = max(du, float(np.abs(eng.getNominalControlSeq() - orc.nominal_control()).max()))
-    return du
 
 
 def _run_one_iteration(case, set_name, K, T, philox):
@@ -420,16 +318,16 @@ def _run_one_iteration(case, set_name, K, T, philox):
     tag = "%s [%s] K=%d T=%d%s" % (case["id"], set_name, K, T, " philox" if philox else "")
     opt = Options(case["model"], ctl, set_name, K, T)
     opt0 = Options(case["model"], ctl, set_name, K, T, zero_coeff=True)
-    cfg, eng, orc, rob = _make(case, K, T, overlay=opt.overlay)
-    cfg0, twin, orc0, rob0 = _make(case, K, T, overlay=opt0.overlay)
+    cfg, eng, orc, rob = make_handles(case, K, T, overlay=opt.overlay)
+    cfg0, twin, orc0, rob0 = make_handles(case, K, T, overlay=opt0.overlay)
     try:
         opt.apply(eng, orc)
         opt0.apply(twin, orc0)
         eps = _compute(case, opt, cfg, [eng], orc, rob, philox, 1)
         _compute(case, opt0, cfg0, [twin], orc0, rob0, philox, 1)
-        _check_form(case, eng, tag)
-        _check_form(case, twin, tag + " [zero coefficient]")
-        du = _check_against_oracle(case, eng, orc, tag)
+        check_form(case, eng, tag)
+        check_form(case, twin, tag + " [zero coefficient]")
+        du = check_against_oracle(case, eng, orc, tag, samples_exact=True)
         print("FIGURE %s: control differs from the oracle by %.3e" % (tag, du))
         assert du <= U_TOL, "%s: u* (or the nominal u*) differs from the oracle by %g" % (tag, du)
 
@@ -437,18 +335,18 @@ def _run_one_iteration(case, set_name, K, T, philox):
         costs, v, u_opt = eng.getSampledCostSeq(), eng.getSampledControls(), eng.getOptimalControlSeq()
         costs0, v0 = twin.getSampledCostSeq(), twin.getSampledControls()
         lo_hi = ranges32(cfg, opt.C)
-        fp = first_pure_rollout(K)
+        fp = first_pure_rollout(K, PURE_PCT)
         lam = cfg["lambda_"]
         for z in range(eng.num_systems):
             if ctl != "robust" and case["model"] not in SAMPLE_RULE_SKIP:
                 want, bound = sample_rule64(opt.mean, opt.sigma[z], opt.eps_of_system(eps, z, cfg.get("colored")), opt.stride,
-                                            fp, lo_hi)
+                                            fp, lo_hi, DECAY)
                 err = np.abs(v[z].astype(np.float64) - want)
                 assert (err <= bound).all(), "%s: system %d sample (k, t, c) = %s is %g from the float64 rule (bound %g)" % (
                     tag, z, np.unravel_index(np.argmax(err - bound), err.shape), float(err.flat[np.argmax(err - bound)]),
                     float(bound.flat[np.argmax(err - bound)]))
             if ctl != "robust" or z == 1:
-                assert _bits_equal(v[z], v0[z]), "%s: system %d samples depend on the likelihood-ratio coefficient" % (tag, z)
+                assert bits_equal(v[z], v0[z]), "%s: system %d samples depend on the likelihood-ratio coefficient" % (tag, z)
                 lr, lr_abs = likelihood_ratio64(v[z], opt.mean, opt.sigma[z], opt.coeff, fp, lam, ALPHA)
                 err = np.abs((costs[z].astype(np.float64) - costs0[z].astype(np.float64)) - lr)
                 bound = likelihood_ratio_bound(T, costs[z], costs0[z], lr_abs)
@@ -458,7 +356,7 @@ def _run_one_iteration(case, set_name, K, T, philox):
             if ctl != "robust":
                 if ctl == "tube" and z == 1 and eng.getStats().nominal_state_used == 0:
                     # tubeSelectKernel: the actual system won the pass, the nominal mean IS the actual one
-                    assert _bits_equal(u_opt[1], u_opt[0]), "%s: nominal u* after a take-over" % tag
+                    assert bits_equal(u_opt[1], u_opt[0]), "%s: nominal u* after a take-over" % tag
                     continue
                 want = softmin64(costs[z], v[z], lam)
                 err = float(np.abs(u_opt[z] - want).max())
@@ -469,18 +367,6 @@ def _run_one_iteration(case, set_name, K, T, philox):
         twin.close()
 
 
-def _make_env(case, K, T, overlay, env):
-    old = os.environ.get(env)
-    os.environ[env] = "1"
-    try:
-        return _make(case, K, T, num_iters=2, overlay=overlay)
-    finally:
-        if old is None:
-            del os.environ[env]
-        else:
-            os.environ[env] = old
-
-
 def _run_two_iterations(case, set_name, K, T, philox):
     """reference-order handle and default fused handle (and, where that one streams its merge, a two-launch twin) through two
     iterations: iteration 1 shapes with decay^1 around the merged mean of iteration 0"""
@@ -488,35 +374,35 @@ def _run_two_iterations(case, set_name, K, T, philox):
     tag = "%s [%s] K=%d T=%d%s two iterations" % (case["id"], set_name, K, T, " philox" if philox else "")
     streams = bool(philox and case["streams"] and (K, T) == KT_STREAMED)
     opt = Options(case["model"], ctl, set_name, K, T)
-    cfg, exact, orc, rob = _make(case, K, T, num_iters=2, overlay=opt.overlay)
+    cfg, exact, orc, rob = make_handles(case, K, T, num_iters=2, overlay=opt.overlay)
     engines = [exact]
     try:
         exact.setReductionMode(m.MPPI_REDUCTION_REFERENCE_ORDER)
-        engines.append(_make(case, K, T, num_iters=2, overlay=opt.overlay)[1])
+        engines.append(make_handles(case, K, T, num_iters=2, overlay=opt.overlay)[1])
         if streams:
-            engines.append(_make_env(case, K, T, opt.overlay, "MPPI_AMD_NO_STREAM_MERGE")[1])
+            engines.append(make_handles(case, K, T, num_iters=2, overlay=opt.overlay, env=dict(MPPI_AMD_NO_STREAM_MERGE="1"))[1])
         opt.apply(exact, orc)
         for e in engines[1:]:
             opt.apply(e)
         _compute(case, opt, cfg, engines, orc, rob, philox, 2)
-        _check_form(case, exact, tag + " [reference-order]")
-        _check_form(case, engines[1], tag + " [fused]", streamed=streams)
-        du = _check_against_oracle(case, exact, orc, tag + " [reference-order]")
+        check_form(case, exact, tag + " [reference-order]")
+        check_form(case, engines[1], tag + " [fused]", streamed=streams)
+        du = check_against_oracle(case, exact, orc, tag + " [reference-order]", samples_exact=True)
         assert du <= U_TOL, "%s [reference-order]: control differs from the oracle by %g" % (tag, du)
         st, ost = exact.getStats(), orc.stats()
         names = (["nominal_sys", "real_sys"] if ctl == "robust" else ["real_sys", "nominal_sys"])[:exact.num_systems]
         for z, name in enumerate(names):
             assert getattr(st, name).baseline == ost["baseline"][z], "%s [reference-order]: %s baseline %r, oracle %r" % (
                 tag, name, getattr(st, name).baseline, ost["baseline"][z])
-        drift = _check_against_oracle(case, engines[1], orc, tag + " [fused]", costs_exact=False)
+        drift = check_against_oracle(case, engines[1], orc, tag + " [fused]", costs_exact=False)
         bound = FUSED_DRIFT.get((case["id"], set_name, (K, T)), U_TOL)
         print("FIGURE %s [fused]: control differs from the oracle by %.3e (bound %.3e)" % (tag, drift, bound))
         assert drift <= bound, "%s [fused]: control differs from the oracle by %g (bound %g; the reference-order handle is exact)" % (
             tag, drift, bound)
         if streams:
-            _check_form(case, engines[2], tag + " [fused, two-launch]")
+            check_form(case, engines[2], tag + " [fused, two-launch]")
             for what in ("getSampledCostSeq", "getOptimalControlSeq", "getControlSeq", "getSampledControls"):
-                assert _bits_equal(getattr(engines[1], what)(), getattr(engines[2], what)()), \
+                assert bits_equal(getattr(engines[1], what)(), getattr(engines[2], what)()), \
                     "%s: %s of the streamed handle differs from the two-launch twin" % (tag, what)
     finally:
         for e in engines:
@@ -541,13 +427,13 @@ def test_colored_handle_refuses_independent_noise(gpu):
     """the colored-noise sampler has one distribution: MPPI_ERR_UNSUPPORTED, and the handle goes on with shared noise"""
     case = next(c for c in CASES if c["controller"] == "colored")
     opt = Options(case["model"], "colored", "table", 65, 3)
-    cfg, eng, orc, _ = _make(case, 65, 3, overlay=opt.overlay)
+    cfg, eng, orc, _ = make_handles(case, 65, 3, overlay=opt.overlay)
     try:
         with pytest.raises(m.MPPIError) as e:
             eng.setIndependentNoise(True)
-        assert e.value.status == MPPI_ERR_UNSUPPORTED, e.value.status
+        assert e.value.status == m.MPPI_ERR_UNSUPPORTED, e.value.status
         opt.apply(eng, orc)
         _compute(case, opt, cfg, [eng], orc, None, False, 1)
-        assert _check_against_oracle(case, eng, orc, case["id"] + " after the refusal") <= U_TOL
+        assert check_against_oracle(case, eng, orc, case["id"] + " after the refusal", samples_exact=True) <= U_TOL
     finally:
         eng.close()

@@ -45,19 +45,16 @@ import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import cartpole_cfg, di_cfg, host_noise, host_spectrum, make_engine, merge_records_numpy, ulp_diff
-from test_kernel_matrix import BUILDERS, _make, _registrations, build_cases
-from test_kernel_sequence import EPS32, FUSED_DRIFT, SOFTMIN_RTOL, _bits_equal, _stats_of, softmin64, stats64
+from common import (PHILOX_SEED, U_TOL, cartpole_cfg, colored_cartpole, di_cfg, host_noise, host_spectrum, make_engine,
+                    merge_records_numpy, ulp_diff)
+from kernel_forms import BUILDERS, FUSED_DRIFT, build_cases, make_handles, registrations
+from restate64 import EPS32, SOFTMIN_RTOL, bits_equal, softmin64, stats64, stats_of
 
-U_TOL = 1e-5
-SEED = 77
 SHAPES = [(8, 8, 2), (126, 2, 3), (1047, 3, 9)]          # (K, world, T), injected noise
 SHAPES_COLORED = SHAPES + [(195, 3, 16), (130, 2, 17)]   # + the radix-4 edges of the colored-noise sampler
 PHILOX_SHAPE = (1600, 8, 12)
 PHILOX_ITERS = 3
 PURE_PCT = 0.01  # common.make_engine / make_oracle default
-MPPI_ERR_INVALID_ARG = 1
-MPPI_ERR_UNSUPPORTED = 10
 UNIT = EPS32 / 2  # u = 2^-24
 
 
@@ -82,7 +79,7 @@ def test_every_registration_has_a_sharded_case(lib):
     # the parametrised list was taken when this module was imported; a test that ran since may have loaded a plugin model
     # into the process-wide registry (tests/test_plugin_model.py), which has no configuration builder
     assert [c["id"] for c in SHARDED_CASES] == [c["id"] for c in runnable if c["model"] in BUILDERS]
-    for name, sampler, _ in _registrations():
+    for name, sampler, _ in registrations():
         prefix = name + ("[colored]" if sampler else "") + "-"
         if any(c["id"].startswith(prefix) for c in runnable):
             assert any(i.startswith(prefix) for i in ids), "registration %s has no sharded case" % prefix
@@ -140,7 +137,7 @@ def test_create_refuses_rollouts_not_divisible_by_the_world(lib):
     for K, rank, world in ((1047, 0, 2), (8, 1, 3), (64, 2, 2), (64, -1, 2)):
         with pytest.raises(m.MPPIError) as e:
             m.VanillaMPPIController("cartpole", K, 5, 0.02, 1.0, rank=rank, world_size=world)
-        assert e.value.status == MPPI_ERR_INVALID_ARG, (K, rank, world, e.value.status)
+        assert e.value.status == m.MPPI_ERR_INVALID_ARG, (K, rank, world, e.value.status)
 
 
 # ---- part B inputs and reference (CPU) ----
@@ -293,7 +290,7 @@ def _run_sharded(case, K, W, T, philox):
     orc = cfg = None
     try:
         for r in range(W):
-            cfg, eng, o, _ = _make(dict(case, kw=dict(case["kw"], rank=r, world_size=W)), K, T)
+            cfg, eng, o, _ = make_handles(dict(case, kw=dict(case["kw"], rank=r, world_size=W)), K, T)
             ranks.append(eng)
             orc = orc or o
         D, C = ranks[0].num_systems, ranks[0].CONTROL_DIM
@@ -306,7 +303,7 @@ def _run_sharded(case, K, W, T, philox):
         noise = None
         if philox:
             for e in ranks:
-                e.setSeed(SEED)
+                e.setSeed(PHILOX_SEED)
         else:
             noise = (host_spectrum(1, K, T, C, seed=K + T) if colored else host_noise(1, K, T, C, seed=K + T))[0]
             for r, e in enumerate(ranks):
@@ -320,9 +317,9 @@ def _run_sharded(case, K, W, T, philox):
             # the mean this iteration samples around: the engine's own, the same bits on every rank
             means = [e.getOptimalControlSeq() for e in ranks]
             for r in range(1, W):
-                assert _bits_equal(means[r], means[0]), "%s rank %d: the mean before the iteration differs from rank 0's" % (tag, r)
+                assert bits_equal(means[r], means[0], nan_equal=True), "%s rank %d: the mean before the iteration differs from rank 0's" % (tag, r)
             if philox:
-                noise = po.philox_spectrum(SEED, g, K, T, C) if colored else po.philox_normal(SEED, g, K, T, C)
+                noise = po.philox_spectrum(PHILOX_SEED, g, K, T, C) if colored else po.philox_normal(PHILOX_SEED, g, K, T, C)
             eps = po.colored_noise(noise, *cfg["colored"], offset_t=1, flavour="engine") if colored else noise
 
             _exchange(ranks)
@@ -358,10 +355,10 @@ def _run_sharded(case, K, W, T, philox):
                 drift = max(drift, float(np.abs(us[r] - chain).max()))
                 if not philox:
                     assert drift <= U_TOL, "%s rank %d: u* differs from the oracle's un-sharded iteration by %g" % (tag, r, drift)
-                assert _bits_equal(us[r], us[0]), "%s rank %d: u* differs from rank 0's" % (tag, r)
+                assert bits_equal(us[r], us[0], nan_equal=True), "%s rank %d: u* differs from rank 0's" % (tag, r)
                 for name in sysnames:
-                    a, b = _stats_of(sts[r], name), _stats_of(sts[0], name)
-                    assert _bits_equal(list(a.values()), list(b.values())), "%s rank %d: %s statistics %s, rank 0 has %s" % (
+                    a, b = stats_of(sts[r], name), stats_of(sts[0], name)
+                    assert bits_equal(list(a.values()), list(b.values()), nan_equal=True), "%s rank %d: %s statistics %s, rank 0 has %s" % (
                         tag, r, name, a, b)
 
             # -------- float64, from the ranks' own dumps
@@ -374,7 +371,7 @@ def _run_sharded(case, K, W, T, philox):
                     err = float(np.abs(us[r][z] - want).max())
                     assert err <= bound, "%s rank %d: system %d u* is %g from the float64 softmin of the ranks' samples (bound %g)" % (
                         tag, r, z, err, bound)
-                    got = _stats_of(sts[r], name)
+                    got = stats_of(sts[r], name)
                     for k in want_st:
                         assert abs(got[k] - want_st[k]) <= bound_st[k], "%s rank %d: %s %s = %r, float64 %r (bound %g)" % (
                             tag, r, name, k, got[k], want_st[k], bound_st[k])
@@ -409,7 +406,7 @@ def _merge_once(eng, rec, D):
     eng.writeRecvRecords(rec)
     eng.iterationMerge()
     st = eng.getStats()
-    return eng.getOptimalControlSeq(), [_stats_of(st, n) for n in ["real_sys", "nominal_sys"][:D]]
+    return eng.getOptimalControlSeq(), [stats_of(st, n) for n in ["real_sys", "nominal_sys"][:D]]
 
 
 @pytest.mark.gpu
@@ -454,9 +451,9 @@ def test_gathered_merge_on_written_records(gpu, problem):
                         if b != dom:
                             rec2[b, :, :TC] = 1e30
                     u2, st2 = _merge_once(eng, rec2, D)
-                    assert _bits_equal(u2, u), "%s: u* changed when the underflowed records' U became 1e30" % tag
+                    assert bits_equal(u2, u, nan_equal=True), "%s: u* changed when the underflowed records' U became 1e30" % tag
                     for z in range(D):
-                        assert _bits_equal(list(st2[z].values()), list(st[z].values())), "%s: system %d statistics changed: %s -> %s" % (
+                        assert bits_equal(list(st2[z].values()), list(st[z].values()), nan_equal=True), "%s: system %d statistics changed: %s -> %s" % (
                             tag, z, st[z], st2[z])
         finally:
             eng.close()
@@ -467,15 +464,14 @@ def test_gathered_merge_on_written_records(gpu, problem):
 def test_caller_driven_iteration_refuses_tsallis_weights_on_a_sharded_handle(gpu):
     """Tsallis weights need the global baseline before any weight, i.e. two exchanges per iteration: the caller-driven pair has
     one, and mppi_iteration_local says so instead of merging weights taken under per-rank baselines"""
-    from test_colored_noise import _colored_cartpole
-    cfg = _colored_cartpole(K=128, T=8)
+    cfg = colored_cartpole(K=128, T=8)
     eng = make_engine(cfg, rank=1, world_size=2)
     try:
         eng.setColoredMPPIParams(gamma=400.0, r_exp=1.7)
         eng.uploadState(cfg["x0"])
         with pytest.raises(m.MPPIError) as e:
             eng.iterationLocal()
-        assert e.value.status == MPPI_ERR_UNSUPPORTED, e.value.status
+        assert e.value.status == m.MPPI_ERR_UNSUPPORTED, e.value.status
         # without them the same handle runs
         eng.setColoredMPPIParams(gamma=0.0, r_exp=0.0)
         eng.iterationLocal()

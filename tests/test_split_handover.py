@@ -4,40 +4,20 @@ beside the rollouts of call N + 1 (csrc/engine_controllers.hip: split_finalize; 
 host-visible result must be the bits the single launch (MPPI_AMD_SPLIT_FINALIZE=0, read when the handle is created) gives:
 controls, state and output trajectories, statistics — with the trajectories read every call, never, or late; with the BAR
 inbox and without; with the smoothing buffer in LDS and in HBM; and with other entry points between the calls."""
-import os
 import time
 
 import numpy as np
 import pytest
 
 from common import autorally_cfg, cartpole_cfg, make_engine
+from kernel_forms import env_override
 
 pytestmark = pytest.mark.gpu
 
 
-class _Env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        for k, v in self.kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def _loop(cfg, env, read_every, cycles=7, between=None):
     """closed loop of `cycles` calls; trajectories fetched on calls where i % read_every == 0 (0: never, only after the loop)"""
-    with _Env(**env):
+    with env_override(**env):
         eng = make_engine(cfg)
     x = cfg["x0"].copy()
     rec = []
@@ -97,7 +77,7 @@ def test_split_equals_single_launch_racer_lstm_steering(gpu):
     """the LSTM-steering RACER model: LSTM state inside the dynamics object, an elevation map, and an output trajectory with NaN
     fields (outputs the model does not produce) — compared bit for bit.  Its re-rollout runs on the model's replicated-lane form
     (finalizeRepKernel) with the default networks, on the two-lane contract form of finalizeKernel otherwise."""
-    from test_racer_dubins_lstm_steering import steering_cfg
+    from racer_cfgs import steering_cfg
     cfg = steering_cfg(K=512, T=40)
     ref = _loop(cfg, {"MPPI_AMD_SPLIT_FINALIZE": "0"}, 2, cycles=5)
     got = _loop(cfg, {"MPPI_AMD_SPLIT_FINALIZE": None}, 2, cycles=5)
@@ -123,7 +103,7 @@ def test_split_equals_single_launch_tube(gpu, num_iters, read_every):
     cfg = di_cfg(K=1024, T=60, tube=True, num_iters=num_iters)
     out = []
     for split in ("0", None):
-        with _Env(MPPI_AMD_SPLIT_FINALIZE=split):
+        with env_override(MPPI_AMD_SPLIT_FINALIZE=split):
             eng = make_engine(cfg)
         x = cfg["x0"].copy()
         rec = []
@@ -149,7 +129,7 @@ def test_split_shortens_the_tube_closed_loop(gpu):
     cfg = di_cfg(K=8192, T=150, tube=True)
     period = {}
     for split in ("0", None):
-        with _Env(MPPI_AMD_SPLIT_FINALIZE=split):
+        with env_override(MPPI_AMD_SPLIT_FINALIZE=split):
             eng = make_engine(cfg)
         x = cfg["x0"].copy()
         for _ in range(30):
@@ -197,7 +177,7 @@ def test_many_unread_calls_then_read(gpu):
     cfg = cartpole_cfg(K=1024, T=100, soft=True)
     out = []
     for split in ("0", None):
-        with _Env(MPPI_AMD_SPLIT_FINALIZE=split):
+        with env_override(MPPI_AMD_SPLIT_FINALIZE=split):
             eng = make_engine(cfg)
         x = cfg["x0"].copy()
         for i in range(40):
@@ -215,7 +195,7 @@ def test_split_shortens_the_closed_loop(gpu):
     cfg = cartpole_cfg(K=16384, T=100)
     period = {}
     for split in ("0", None):
-        with _Env(MPPI_AMD_SPLIT_FINALIZE=split):
+        with env_override(MPPI_AMD_SPLIT_FINALIZE=split):
             eng = make_engine(cfg)
         x = cfg["x0"].copy()
         for _ in range(50):

@@ -5,28 +5,22 @@ combineKernel.  The reference has no such stage to compare with (it launches rol
 iteration, controllers/MPPI/mppi_controller.cu:128-236); what the test pins is that the streamed form is the SAME FUNCTION as
 the two-launch form — every u*, every statistic, every trajectory cost, bit for bit — and that it really is the form that ran.
 """
-import os
 
 import numpy as np
 import pytest
 
 from common import cartpole_cfg, cartpole_cfg_lr, di_cfg, make_engine, make_oracle
+from restate64 import bits
+from kernel_forms import env_override
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _pair(cfg, **kw):
     """(streamed handle, two-launch handle) of the same configuration; the switch is read at mppi_create"""
     streamed = make_engine(cfg, **kw)
-    os.environ["MPPI_AMD_NO_STREAM_MERGE"] = "1"
-    try:
+    with env_override(MPPI_AMD_NO_STREAM_MERGE="1"):
         plain = make_engine(cfg, **kw)
-    finally:
-        del os.environ["MPPI_AMD_NO_STREAM_MERGE"]
     return streamed, plain
 
 
@@ -52,9 +46,9 @@ def test_streamed_merge_is_the_two_launch_iteration(gpu, cfg):
     for step in range(6):
         a.computeControl(x, 1)
         b.computeControl(x, 1)
-        assert np.array_equal(_bits(a.getControlSeq()), _bits(b.getControlSeq())), step
-        assert np.array_equal(_bits(_stats(a)), _bits(_stats(b))), step
-        assert np.array_equal(_bits(a.getSampledCostSeq()), _bits(b.getSampledCostSeq())), step
+        assert np.array_equal(bits(a.getControlSeq()), bits(b.getControlSeq())), step
+        assert np.array_equal(bits(_stats(a)), bits(_stats(b))), step
+        assert np.array_equal(bits(a.getSampledCostSeq()), bits(b.getSampledCostSeq())), step
         x, _ = a.modelStep(x, a.getControlSeq()[0])
         a.slideControlSequence(1)
         b.slideControlSequence(1)
@@ -89,15 +83,15 @@ def test_streamed_merge_optimize_and_settings_between_launches(gpu):
     for e in (a, b):
         e.uploadState(cfg["x0"])
         e.optimize(7)
-    assert np.array_equal(_bits(a.getControlSeq()), _bits(b.getControlSeq()))
-    assert np.array_equal(_bits(_stats(a)), _bits(_stats(b)))
+    assert np.array_equal(bits(a.getControlSeq()), bits(b.getControlSeq()))
+    assert np.array_equal(bits(_stats(a)), bits(_stats(b)))
     # the reference-order reduction does not stream: the handle must fall back to two launches and stay equal to its twin
     for e in (a, b):
         e.setReductionMode(m.MPPI_REDUCTION_REFERENCE_ORDER)
         e.optimize(3)
         e.setReductionMode(m.MPPI_REDUCTION_FUSED)
         e.optimize(2)
-    assert np.array_equal(_bits(a.getControlSeq()), _bits(b.getControlSeq()))
+    assert np.array_equal(bits(a.getControlSeq()), bits(b.getControlSeq()))
     a.close()
     b.close()
 

@@ -12,12 +12,11 @@ import pytest
 
 import mppi_generic_amd as m
 import pyoracle as po
-from common import cartpole_cfg, make_oracle
+from common import U_TOL, cartpole_cfg, make_oracle
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(REPO, "examples", "_build")
 NAME = "templated_cartpole_nln"
-U_TOL = 1e-5
 K, T, SIGMA, SEED = 1024, 30, 0.8, 42  # the example's ROLLOUTS, HORIZON, std_dev and the templated controllers' default seed
 
 

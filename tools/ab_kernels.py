@@ -71,10 +71,7 @@ def main():
         cfg["colored"] = ([1.0, 1.0], 0.97, 0.0)
         res["lstm_colored_65536x200"] = vanilla(cfg, 10, passes=3)
     if "racer" in which:
-        from test_racer_dubins_elevation import elevation_cfg
-        from test_racer_dubins_lstm_steering import steering_cfg
-        from test_racer_dubins_lstm_unc import uncertainty_cfg
-        from test_racer_dubins_suspension import suspension_cfg
+        from racer_cfgs import elevation_cfg, steering_cfg, uncertainty_cfg, suspension_cfg
         res["racer_elevation_16384x100"] = vanilla(elevation_cfg(K=16384, T=100), 50, passes=3)
         res["racer_lstm_steering_16384x100"] = vanilla(steering_cfg(K=16384, T=100), 40, passes=3)
         res["racer_suspension_16384x100"] = vanilla(suspension_cfg(K=16384, T=100), 40, passes=3)
@@ -95,15 +92,13 @@ def main():
         cfg["ranges"] = [[-3.0, 3.0], [-3.0, 3.0]]
         res["robust_di_8192x150"] = robust(cfg, 25.0, 50)
     if "robust_racer_all" in which:
-        from test_racer_dubins_elevation import elevation_cfg
-        from test_racer_dubins_lstm_steering import steering_cfg
-        from test_racer_dubins_suspension import suspension_cfg
+        from racer_cfgs import elevation_cfg, steering_cfg, suspension_cfg
         for name, mk in (("elevation", elevation_cfg), ("lstm_steering", steering_cfg), ("suspension", suspension_cfg)):
             cfg = mk(K=16384, T=100, D=2)
             cfg["control_cost_coeff"] = [0.2, 0.1]
             res["robust_racer_%s_16384x100" % name] = robust(cfg, 2000.0, 10, passes=3)
     if "robust_racer" in which:
-        from test_racer_dubins_lstm_unc import uncertainty_cfg
+        from racer_cfgs import uncertainty_cfg
         cfg = uncertainty_cfg(K=16384, T=100, D=2)
         cfg["control_cost_coeff"] = [0.2, 0.1]
         res["robust_racer_complete_16384x100"] = robust(cfg, 2000.0, 10, passes=3)

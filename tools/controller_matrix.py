@@ -11,10 +11,7 @@ for p in (REPO, os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
 import numpy as np  # noqa: E402
 import mppi_generic_amd as m  # noqa: E402
 from common import autorally_cfg, bicycle_lstm_cfg, cartpole_cfg, di_cfg, make_engine, racer_cfg  # noqa: E402
-from test_racer_dubins_elevation import elevation_cfg as _elev  # noqa: E402
-from test_racer_dubins_lstm_steering import steering_cfg as _steer  # noqa: E402
-from test_racer_dubins_suspension import suspension_cfg as _susp  # noqa: E402
-from test_racer_dubins_lstm_unc import uncertainty_cfg as _unc  # noqa: E402
+from racer_cfgs import elevation_cfg as _elev, steering_cfg as _steer, suspension_cfg as _susp, uncertainty_cfg as _unc  # noqa: E402
 
 MODELS = {
     "cartpole": lambda: cartpole_cfg(K=16384, T=100),

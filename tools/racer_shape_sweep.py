@@ -10,10 +10,7 @@ for p in (REPO, os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
     sys.path.insert(0, p)
 import numpy as np  # noqa: E402
 from common import host_noise, make_engine, make_oracle, ulp_diff  # noqa: E402
-from test_racer_dubins_elevation import elevation_cfg  # noqa: E402
-from test_racer_dubins_lstm_steering import steering_cfg  # noqa: E402
-from test_racer_dubins_lstm_unc import uncertainty_cfg  # noqa: E402
-from test_racer_dubins_suspension import suspension_cfg  # noqa: E402
+from racer_cfgs import elevation_cfg, steering_cfg, uncertainty_cfg, suspension_cfg  # noqa: E402
 
 MODELS = {"elevation": elevation_cfg, "lstm_steering": steering_cfg, "suspension": suspension_cfg, "complete": uncertainty_cfg}
 trials = int(sys.argv[1]) if len(sys.argv) > 1 else 40

@@ -15,10 +15,7 @@ for p in (REPO, os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
     sys.path.insert(0, p)
 import numpy as np  # noqa: E402
 from common import host_noise, make_engine  # noqa: E402
-from test_racer_dubins_elevation import elevation_cfg  # noqa: E402
-from test_racer_dubins_lstm_steering import steering_cfg  # noqa: E402
-from test_racer_dubins_lstm_unc import uncertainty_cfg  # noqa: E402
-from test_racer_dubins_suspension import suspension_cfg  # noqa: E402
+from racer_cfgs import elevation_cfg, steering_cfg, uncertainty_cfg, suspension_cfg  # noqa: E402
 
 target = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
 MODELS = (("elevation", elevation_cfg, [(64, 4)]), ("lstm_steering", steering_cfg, [(64, 4)]),

@@ -14,8 +14,7 @@ for p in (REPO, os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
     sys.path.insert(0, p)
 import numpy as np  # noqa: E402
 import mppi_generic_amd as m  # noqa: E402
-from common import host_noise  # noqa: E402
-import test_rmppi as tr  # noqa: E402
+from common import gains, host_noise, make_pair, rm_cfg  # noqa: E402
 
 target = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 MODELS = ("elevation", "lstm_steering", "suspension", "complete", "autorally", "lstm", "di")
@@ -25,11 +24,11 @@ total = nonfinite = mismatches = fused_diff = 0
 t0 = time.time()
 report = {}
 for name in MODELS:
-    cfg = tr._rm_cfg(name, K=K, T=T)
+    cfg = rm_cfg(name, K=K, T=T)
     engines = {}
     for variant in (m.MPPI_KERNEL_PIPELINE, m.MPPI_KERNEL_FUSED):
-        eng, _, _ = tr._make_pair(cfg, thr=40.0, kernel_variant=variant)
-        eng.setFeedbackGains(tr._gains(T, eng.STATE_DIM, eng.CONTROL_DIM), False)
+        eng, _, _ = make_pair(cfg, thr=40.0, kernel_variant=variant)
+        eng.setFeedbackGains(gains(T, eng.STATE_DIM, eng.CONTROL_DIM), False)
         engines[variant] = eng
     S = engines[m.MPPI_KERNEL_PIPELINE].STATE_DIM
     dx = np.zeros(S, np.float32)

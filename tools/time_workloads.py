@@ -58,15 +58,14 @@ if "lstm" in which:
     run("cartpole+colored", cfg, [(64, 1, 1), (64, 1, 2)], n=50)
 if "racer" in which:
     from common import racer_cfg  # noqa: E402
-    from test_racer_dubins_elevation import elevation_cfg  # noqa: E402
-    from test_racer_dubins_lstm_steering import steering_cfg  # noqa: E402
+    from racer_cfgs import elevation_cfg, steering_cfg  # noqa: E402
     run("racer", racer_cfg(K=16384, T=100), [(64, 1, 1), (64, 1, 2)], n=50)
     run("racer-elev", elevation_cfg(K=16384, T=100), [(64, 1, 1), (64, 1, 2), (64, 4, 1), (64, 4, 2)], n=50)
     run("racer-flat", elevation_cfg(K=16384, T=100, with_map=False), [(64, 1, 2)], n=50)
     run("racer-lstm", steering_cfg(K=16384, T=100), [(64, 1, 1), (64, 4, 1), (64, 4, 2)], n=50)
-    from test_racer_dubins_suspension import suspension_cfg  # noqa: E402
+    from racer_cfgs import suspension_cfg  # noqa: E402
     run("racer-suspension", suspension_cfg(K=16384, T=100), [(64, 1, 1), (64, 4, 1), (64, 4, 2)], n=30)
-    from test_racer_dubins_lstm_unc import uncertainty_cfg  # noqa: E402
+    from racer_cfgs import uncertainty_cfg  # noqa: E402
     run("racer-uncertainty", uncertainty_cfg(K=16384, T=100), [(64, 1, 1), (64, 4, 1), (64, 4, 2)], n=30)
     cfg = steering_cfg(K=16384, T=100)
     cfg["colored"] = ([1.0, 1.0], 0.97, 0.0)
