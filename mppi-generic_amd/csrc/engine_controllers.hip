@@ -41,34 +41,44 @@ mppi_status mppi_inject_noise(mppi_handle h, const float* eps, int n_iters)
   return MPPI_OK;
 }
 
+/** The one staging rule: system z's initial state, nominal control and control history go to slot z of an input block the host
+ *  writes (`in`: the inbox, the pinned block).  The initial states are the system table's, x_measured where it names none; a
+ *  null `mean` / `history` table leaves those slices as they are. */
+static inline void stageInputs(mppi_handle h, float* in, const float* x_measured, const std::vector<float>* const mean[2],
+                               const std::vector<float>* const history[2], int history_stride)
+{
+  for (int z = 0; z < h->D; z++)
+  {
+    const float* x = h->sys.x0[z] ? h->sys.x0[z]->data() : x_measured;
+    std::copy(x, x + h->S, inSlice(in, h->in.x0) + z * h->S);
+    if (mean)
+      std::copy(mean[z]->begin(), mean[z]->end(), inSlice(in, h->in.mean) + z * h->TC);
+    if (history && history[z])
+      std::copy(history[z]->begin(), history[z]->end(), inSlice(in, h->in.history) + z * history_stride);
+  }
+}
+
 static mppi_status uploadTube(mppi_handle h, const float* x0_actual)
 {
   // both initial states and both nominal controls through the pinned input block: one copy
-  float* in = h->in_pin_h;
-  std::copy(x0_actual, x0_actual + h->S, in);
-  std::copy(h->tube_x_h.begin(), h->tube_x_h.end(), in + h->S);
-  float* mean = in + (h->mean_d - h->in_block_d);
-  std::copy(h->control_h.begin(), h->control_h.end(), mean);
-  std::copy(h->nominal_control_h.begin(), h->nominal_control_h.end(), mean + h->TC);
-  const size_t n = (size_t)(h->mean_d - h->in_block_d) + 2 * (size_t)h->TC;
-  HIP_TRY(h, hipMemcpyAsync(h->in_block_d, in, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+  stageInputs(h, h->in_pin_h, x0_actual, h->sys.control, nullptr, 0);
+  const size_t n = h->in.mean.floats + 2 * (size_t)h->TC;
+  HIP_TRY(h, hipMemcpyAsync(h->in_block_d, h->in_pin_h, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
   return MPPI_OK;
 }
 
 /** stats of system z from the floats the merge kernel wrote */
 void parseStats(mppi_handle h, const float* st)
 {
-  mppi_system_stats* sys[2] = { &h->stats_h.real_sys, &h->stats_h.nominal_sys };
-  if (h->cfg.controller == MPPI_CONTROLLER_ROBUST)  // system 0 is the NOMINAL one there (robust_mppi_controller.cu:637-640)
-    std::swap(sys[0], sys[1]);
   for (int z = 0; z < h->D; z++)
   {
     const float* s = st + z * kernels::STATS_STRIDE;
-    sys[z]->baseline = s[0];
-    sys[z]->normalizer = s[1];
-    sys[z]->free_energy_mean = s[2];
-    sys[z]->free_energy_variance = s[3];
-    sys[z]->free_energy_modified_variance = s[4];
+    mppi_system_stats* sys = h->sys.stats[z];
+    sys->baseline = s[0];
+    sys->normalizer = s[1];
+    sys->free_energy_mean = s[2];
+    sys->free_energy_variance = s[3];
+    sys->free_energy_modified_variance = s[4];
     if (s[6] != 0.0f)  // combineKernel gave up waiting for a peer's record (P2P exchange)
       h->exchange_failed = true;
   }
@@ -97,95 +107,174 @@ static inline void launchIngest(mppi_handle h)
   hipLaunchKernelGGL(kernels::ingestKernel, dim3(1), dim3(256), 0, h->stream, h->io_in_h.dev(), h->in_block_d, (int)h->in_floats);
 }
 
-/** spins on a flag the finalize kernel raises in host memory; falls back to a stream synchronisation when the flag does not
- *  show within the limit (a failed launch, a wedged device): the caller then sees the HIP error instead of a hang */
+/** spins on io_flags[idx] until reached(value); falls back to a stream synchronisation (the side stream's, and the handle's when
+ *  `sync_stream`) when the flag does not show within the limit (a failed launch, a wedged device): the caller then sees the HIP
+ *  error, or `what`, instead of a hang */
+template <class Reached>
+static inline mppi_status spinOnFlag(mppi_handle h, int idx, Reached reached, bool sync_stream, const char* what)
+{
+  using clock = std::chrono::steady_clock;
+  const clock::time_point t0 = clock::now();
+  volatile unsigned* flag = h->io_flags_h + idx;
+  unsigned spins = 0;
+  while (!reached(__atomic_load_n(flag, __ATOMIC_ACQUIRE)))
+  {
+#if defined(__x86_64__)
+    __builtin_ia32_pause();
+#endif
+    if ((++spins & 0x3ff) == 0 && std::chrono::duration<double>(clock::now() - t0).count() > 2.0)
+    {
+      if (sync_stream)
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+      if (h->side_stream)
+        HIP_TRY(h, hipStreamSynchronize(h->side_stream));
+      if (!reached(__atomic_load_n(flag, __ATOMIC_ACQUIRE)))
+        return fail(h, MPPI_ERR_HIP, what);
+      break;
+    }
+  }
+  return MPPI_OK;
+}
+
+/** a flag the finalize kernel (or raiseFlagKernel) raises in host memory shows hand-over `seq` */
 static mppi_status waitHostFlag(mppi_handle h, int idx, unsigned seq)
 {
-  using clock = std::chrono::steady_clock;
-  const clock::time_point t0 = clock::now();
-  volatile unsigned* flag = h->io_flags_h + idx;
-  unsigned spins = 0;
-  while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq)
-  {
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-    if ((++spins & 0x3ff) == 0 && std::chrono::duration<double>(clock::now() - t0).count() > 2.0)
-    {
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-      if (h->side_stream)
-        HIP_TRY(h, hipStreamSynchronize(h->side_stream));
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq)
-        return fail(h, MPPI_ERR_HIP, "the finalize kernel finished without raising its hand-over flag");
-      break;
-    }
-  }
-  return MPPI_OK;
+  return spinOnFlag(h, idx, [seq](unsigned v) { return v == seq; }, true,
+                    "the finalize kernel finished without raising its hand-over flag");
 }
 
-/** the same for "the flag has reached seq" (sequence numbers only grow; wrap-around safe): the trajectory phases of a split
- *  hand-over run in order on the side stream, so a later call's flag value covers the earlier ones */
+/** the flag has reached seq (sequence numbers only grow; wrap-around safe): the trajectory phases of a split hand-over run in
+ *  order on the side stream, so a later call's flag value covers the earlier ones */
 static mppi_status waitHostFlagReached(mppi_handle h, int idx, unsigned seq)
 {
-  using clock = std::chrono::steady_clock;
-  const clock::time_point t0 = clock::now();
-  volatile unsigned* flag = h->io_flags_h + idx;
-  unsigned spins = 0;
-  while ((int)(__atomic_load_n(flag, __ATOMIC_ACQUIRE) - seq) < 0)
-  {
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-    if ((++spins & 0x3ff) == 0 && std::chrono::duration<double>(clock::now() - t0).count() > 2.0)
-    {
-      if (h->side_stream)
-        HIP_TRY(h, hipStreamSynchronize(h->side_stream));
-      if ((int)(__atomic_load_n(flag, __ATOMIC_ACQUIRE) - seq) < 0)
-        return fail(h, MPPI_ERR_HIP, "the trajectory phase of an earlier call finished without raising its flag");
-      break;
-    }
-  }
-  return MPPI_OK;
+  return spinOnFlag(h, idx, [seq](unsigned v) { return (int)(v - seq) >= 0; }, false,
+                    "the trajectory phase of an earlier call finished without raising its flag");
 }
 
-/** the state / output trajectories of the last low-latency computeControl: wait for the finalize kernel's second flag */
+/** everything enqueued on the handle's stream so far is done: a flag raised behind it that the host spins on (`counter`: the
+ *  flag's own hand-over count), or — MPPI_AMD_NO_SPIN=1 — a stream synchronisation */
+static mppi_status streamRoundTrip(mppi_handle h, int idx, unsigned& counter)
+{
+  if (!h->low_latency)
+  {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MPPI_OK;
+  }
+  const unsigned seq = ++counter;
+  hipLaunchKernelGGL(kernels::raiseFlagKernel, dim3(1), dim3(64), 0, h->stream, h->io_flags_h.dev() + idx, seq);
+  HIP_TRY(h, hipGetLastError());
+  return waitHostFlag(h, idx, seq);
+}
+
+/** the state / output trajectories of the last low-latency computeControl: wait for the finalize kernel's second flag of every
+ *  system, then take the state sequences through the system table */
 static mppi_status ensureTrajectories(mppi_handle h)
 {
   if (!h->traj_pending)
     return MPPI_OK;
   MPPI_TRY(waitHostFlag(h, 1, h->io_seq));
-  const int T = h->cfg.num_timesteps;
-  const float* out = h->io_out_h;
-  if (h->cfg.controller == MPPI_CONTROLLER_ROBUST)
-  {  // system 0: the nominal trajectory (the next call's candidates start from it), system 1: the real one
+  if (h->D == 2)
     MPPI_TRY(waitHostFlag(h, 3, h->io_seq));
-    h->traj_pending = false;
-    const float* xs = out + (h->state_out_d - h->out_block_d);
-    std::copy(xs, xs + (size_t)T * h->S, h->nominal_state_h.begin());
-    std::copy(xs + (size_t)T * h->S, xs + (size_t)2 * T * h->S, h->state_h.begin());
-    if (!allFinite(h->nominal_state_h))
-      return fail(h, MPPI_ERR_NAN, "non-finite value in the nominal state sequence of the last mppi_compute_control");
-    return MPPI_OK;
-  }
-  if (h->cfg.controller == MPPI_CONTROLLER_TUBE)
-  {  // system 0: the actual system, system 1: the nominal one (its first state is where the next call starts from)
-    MPPI_TRY(waitHostFlag(h, 3, h->io_seq));
-    h->traj_pending = false;
-    const float* xs = out + (h->state_out_d - h->out_block_d);
-    std::copy(xs, xs + (size_t)T * h->S, h->state_h.begin());
-    std::copy(xs + (size_t)T * h->S, xs + (size_t)2 * T * h->S, h->nominal_state_h.begin());
-    if (!allFinite(h->state_h) || !allFinite(h->nominal_state_h))
-      return fail(h, MPPI_ERR_NAN, "non-finite value in the state sequences of the last mppi_compute_control");
-    return MPPI_OK;
-  }
   h->traj_pending = false;
-  std::copy(out + (h->state_out_d - h->out_block_d), out + (h->state_out_d - h->out_block_d) + (size_t)T * h->S,
-            h->state_h.begin());
-  if (!allFinite(h->state_h))  // base_plant.hpp:515-528 checks the state trajectory as well as the control
+  const size_t n = (size_t)h->cfg.num_timesteps * h->S;
+  const float* xs = outSlice(h->io_out_h, h->out.state);
+  for (int z = 0; z < h->D; z++)
+    std::copy(xs + z * n, xs + (z + 1) * n, h->sys.state[z]->begin());
+  // base_plant.hpp:515-528 checks the state trajectory as well as the control.  Robust: the nominal trajectory only (system 0:
+  // the next call's candidates start from it); Tube: both (the nominal one's first state is where the next call starts from)
+  if (h->cfg.controller == MPPI_CONTROLLER_ROBUST && !allFinite(h->nominal_state_h))
+    return fail(h, MPPI_ERR_NAN, "non-finite value in the nominal state sequence of the last mppi_compute_control");
+  if (h->cfg.controller == MPPI_CONTROLLER_TUBE && (!allFinite(h->state_h) || !allFinite(h->nominal_state_h)))
+    return fail(h, MPPI_ERR_NAN, "non-finite value in the state sequences of the last mppi_compute_control");
+  if (h->D == 1 && !allFinite(h->state_h))
     return fail(h, MPPI_ERR_NAN, "non-finite value in the state sequence of the last mppi_compute_control");
   return MPPI_OK;
 }
 
+/** points a finalize pass at the device-mapped outbox and takes the next hand-over sequence number; stats_systems: how many
+ *  systems' merge statistics travel with the control sequences (0: a pass that only re-rolls a trajectory) */
+static inline void toOutbox(mppi_handle h, kernels::FinalizeArgs& a, int stats_systems)
+{
+  float* out = h->io_out_h.dev();
+  a.control_out_d = outSlice(out, h->out.control);
+  a.state_out_d = outSlice(out, h->out.state);
+  a.output_out_d = outSlice(out, h->out.output);
+  if (stats_systems > 0)
+  {
+    a.stats_in_d = h->stats_d;
+    a.stats_out_d = outSlice(out, h->out.stats);
+    a.stats_floats = stats_systems * kernels::STATS_STRIDE;
+  }
+  a.flags_d = h->io_flags_h.dev();
+  a.seq = ++h->io_seq;
+}
+
+/** Launches the finalize pass `a` (pointed at the outbox) for num_systems systems and marks the outbox as holding the results.
+ *  One launch — or, split hand-over (mppi_handle_s::split_finalize), two.  The control phase runs on the handle's stream, as
+ *  kernels::mergeControlKernel when `merge` brings the last rollout launch's un-merged records along; it leaves a copy of the
+ *  input block carry_src_d in this call's carry block.  The trajectory phase runs on the side stream: it waits for the carry block
+ *  by itself (no event between the streams) and reads nothing else.  a.carry_d is that block afterwards. */
+static mppi_status launchHandover(mppi_handle h, kernels::FinalizeArgs& a, int num_systems, const float* carry_src_d,
+                                  const kernels::MergeControlArgs* merge)
+{
+  std::string err;
+  if (h->split_finalize)
+  {
+    // this call's carry block was last read by the trajectory phase of the call two hand-overs ago: its flags are up, or we wait
+    const unsigned p = a.seq & 1u;
+    if (h->carry_seq[p] != 0)
+      for (int z = 0; z < num_systems; z++)
+        MPPI_TRY(waitHostFlagReached(h, 2 * z + 1, h->carry_seq[p]));
+    a.phases = 1;
+    a.carry_d = h->carry_d + (size_t)p * h->in_floats;
+    a.carry_src_d = carry_src_d;
+    a.carry_floats = (int)h->in_floats;
+    a.carry_mean_off = (int)h->in.mean.floats;
+    a.carry_ready_d = reinterpret_cast<unsigned*>(h->carry_d + 2 * h->in_floats) + 2 * p;
+  }
+  const mppi_status st = merge ? h->model->launchMergeControl(a, *merge, h->stream, err) :
+                                 h->model->launchFinalize(num_systems, a, h->stream, err);
+  if (st != MPPI_OK)
+    return fail(h, st, err);
+  if (h->split_finalize)
+  {
+    kernels::FinalizeArgs b = a;
+    b.phases = 2;
+    b.carry_d = nullptr;
+    b.control_in_d = inSlice(a.carry_d, h->in.mean);
+    b.x0_d = inSlice(a.carry_d, h->in.x0);
+    b.smooth_mask = 0;
+    b.scratch_d = h->fin_scratch2_d;
+    const mppi_status st2 = h->model->launchFinalize(num_systems, b, h->side_stream, err);
+    if (st2 != MPPI_OK)
+      return fail(h, st2, err);
+    HIP_TRY(h, hipEventRecord(h->ev_side, h->side_stream));
+    h->side_pending = true;
+    h->carry_seq[a.seq & 1u] = a.seq;
+  }
+  h->out_pin_fresh = false;
+  h->results_in_io = true;
+  h->traj_pending = true;  // set before the waits: a failing wait must not leave io_out unguarded for the next call
+  return MPPI_OK;
+}
+
+/** The control sequences and the merge statistics of hand-over io_seq are out (flag 0, and flag 2 of a second system): take
+ *  them through the system table.  after_wait(): what the caller does between the waits and the copies (Vanilla's host stamp). */
+template <class AfterWait>
+static inline mppi_status takeControls(mppi_handle h, AfterWait after_wait)
+{
+  for (int z = 0; z < h->D; z++)
+    MPPI_TRY(waitHostFlag(h, 2 * z, h->io_seq));
+  after_wait();
+  const float* u = outSlice(h->io_out_h, h->out.control);
+  for (int z = 0; z < h->D; z++)
+    std::copy(u + (size_t)z * h->TC, u + (size_t)(z + 1) * h->TC, h->sys.control[z]->begin());
+  parseStats(h, outSlice(h->io_out_h, h->out.stats));
+  h->stats_h_fresh = true;
+  return MPPI_OK;
+}
+
+/** reference: controllers/MPPI/mppi_controller.cu:152-231; ColoredMPPI/colored_mppi_controller.cu:150-237 */
 static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, int stride)
 {
   const int T = h->cfg.num_timesteps;
@@ -202,19 +291,7 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
     h->model->hostEnforceLeash(x0_true, &h->state_h[(size_t)h->leash_jump * h->S], h->leash_dist.data(), leashed.data());
     x0 = leashed.data();
   }
-  kernels::FinalizeArgs a{};
-  a.scratch_d = h->fin_scratch_d;
-  a.control_in_d = h->mean_d;
-  a.history_d = h->history_d;
-  a.history_stride = 0;
-  a.x0_d = h->x0_d;
-  a.dt = h->cfg.dt;
-  a.num_timesteps = T;
-  a.smooth_mask = 1;
-  a.constrain_mask = 1;
-  // ColoredMPPI clamps only control channel 1 after smoothing (colored_mppi_controller.cu:232-237)
-  a.constrain_mode = h->cfg.controller == MPPI_CONTROLLER_COLORED ? 1 : 0;
-  std::string err;
+  kernels::FinalizeArgs a = finalizeArgs(h, h->mean_d, 0, /*smooth*/ 1, /*constrain*/ 1);
   if (h->low_latency)
   {
     /* Inputs and results travel through host memory mapped into the device: no copy command, no stream synchronisation.
@@ -231,10 +308,7 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
     auto stamp = [&](int i) {
       h->host_stamps_us[i] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count();
     };
-    float* in = h->io_in_h;
-    std::copy(x0, x0 + h->S, in + (h->x0_d - h->in_block_d));
-    std::copy(h->control_h.begin(), h->control_h.end(), in + (h->mean_d - h->in_block_d));
-    std::copy(h->history_h.begin(), h->history_h.end(), in + (h->history_d - h->in_block_d));
+    stageInputs(h, h->io_in_h, x0, h->sys.control, h->sys.history, 0);
     stamp(0);
     // BAR inbox: no ingest launch — the kernels of this call read the inbox (device memory the stores above went to) themselves
     const bool direct = h->bar_inbox && h->cfg.num_iters >= 1 && h->reduction_mode == MPPI_REDUCTION_FUSED && !tsallisActive(h) &&
@@ -250,10 +324,10 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
     if (direct)
     {
       publishInbox(h);  // the write-combined stores are out before the doorbell of the first launch
-      h->x0_src_d = h->io_in_h.dev() + (h->x0_d - h->in_block_d);
-      h->mean_src_d = h->io_in_h.dev() + (h->mean_d - h->in_block_d);
+      h->x0_src_d = inSlice(h->io_in_h.dev(), h->in.x0);
+      h->mean_src_d = inSlice(h->io_in_h.dev(), h->in.mean);
       a.x0_d = h->x0_src_d;
-      a.history_d = h->io_in_h.dev() + (h->history_d - h->in_block_d);
+      a.history_d = inSlice(h->io_in_h.dev(), h->in.history);
     }
     else
     {
@@ -277,33 +351,11 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
     else
       MPPI_TRY(flushMerge(h));
     stamp(3);
-    a.control_out_d = h->io_out_h.dev() + (h->ctrl_out_d - h->out_block_d);
-    a.state_out_d = h->io_out_h.dev() + (h->state_out_d - h->out_block_d);
-    a.output_out_d = h->io_out_h.dev() + (h->output_out_d - h->out_block_d);
-    a.stats_in_d = h->stats_d;
-    a.stats_out_d = h->io_out_h.dev() + (h->stats_d - h->out_block_d);
-    a.stats_floats = kernels::STATS_STRIDE;
-    a.flags_d = h->io_flags_h.dev();
-    a.seq = ++h->io_seq;
-    float* carry = nullptr;
-    if (h->split_finalize)
-    {
-      // this call's carry block was last read by the trajectory phase of the call two hand-overs ago: its flag is up, or we wait
-      const unsigned p = a.seq & 1u;
-      if (h->carry_seq[p] != 0)
-        MPPI_TRY(waitHostFlagReached(h, 1, h->carry_seq[p]));
-      carry = h->carry_d + (size_t)p * h->in_floats;
-      a.phases = 1;
-      a.carry_d = carry;
-      a.carry_src_d = direct ? h->io_in_h.dev() : h->in_block_d;
-      a.carry_floats = (int)h->in_floats;
-      a.carry_mean_off = (int)(h->mean_d - h->in_block_d);
-      a.carry_ready_d = reinterpret_cast<unsigned*>(h->carry_d + 2 * h->in_floats) + 2 * p;
-    }
+    toOutbox(h, a, 1);
+    // (x0 and the control history: the slices on either side of the mean)
     auto ingest_ranges = [&](const float* src) -> mppi_status {
       hipLaunchKernelGGL(kernels::ingestRangesKernel, dim3(1), dim3(256), 0, h->stream, src, h->in_block_d,
-                         (int)(h->mean_d - h->in_block_d), (int)(h->history_d - h->in_block_d),
-                         (int)(h->in_floats - (size_t)(h->history_d - h->in_block_d)));
+                         (int)h->in.mean.floats, (int)h->in.history.floats, (int)(h->in_floats - h->in.history.floats));
       HIP_TRY(h, hipGetLastError());
       return MPPI_OK;
     };
@@ -313,10 +365,9 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
     // touches neither what the finalize kernel reads (inbox, mean_d) nor what it writes.
     if (direct && !h->split_finalize)
       MPPI_TRY(ingest_ranges(h->io_in_h.dev()));
-    mppi_status st;
+    kernels::MergeControlArgs m{};
     if (fuse_records)
     {
-      kernels::MergeControlArgs m{};
       m.records_t_d = recordsTransposed(h, const_cast<float*>(fuse_records));
       m.num_records = h->num_blocks;
       m.lambda = h->cfg.lambda;
@@ -324,45 +375,16 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
       m.mean_out_d = h->mean_d;
       m.stats_d = h->stats_d;
       h->n_merge_launches++;  // (the merge of this call: inside the control phase's launch)
-      st = h->model->launchMergeControl(a, m, h->stream, err);
     }
-    else
-      st = h->model->launchFinalize(1, a, h->stream, err);
-    if (st != MPPI_OK)
-      return fail(h, st, err);
-    if (h->split_finalize)
-    {  // the trajectory phase, on the side stream: it waits for the control phase's carry block by itself (no event between the
-       // streams), and reads nothing else
-      kernels::FinalizeArgs b = a;
-      b.phases = 2;
-      b.carry_d = nullptr;
-      b.control_in_d = carry + (h->mean_d - h->in_block_d);
-      b.x0_d = carry + (h->x0_d - h->in_block_d);
-      b.smooth_mask = 0;
-      b.scratch_d = h->fin_scratch2_d;
-      const mppi_status st2 = h->model->launchFinalize(1, b, h->side_stream, err);
-      if (st2 != MPPI_OK)
-        return fail(h, st2, err);
-      HIP_TRY(h, hipEventRecord(h->ev_side, h->side_stream));
-      h->side_pending = true;
-      h->carry_seq[a.seq & 1u] = a.seq;
-    }
+    MPPI_TRY(launchHandover(h, a, 1, direct ? h->io_in_h.dev() : h->in_block_d, fuse_records ? &m : nullptr));
     if (direct && h->split_finalize)
     {  // behind the control phase, off the caller's path: the device-resident x0 / history later mppi_optimize / operator calls
        // read — from the CARRY block (the host may be rewriting the inbox for its next call by now; the carry block of this parity
        // is not rewritten before the call after next, which first waits for this call's flag 1)
-      MPPI_TRY(ingest_ranges(carry));
+      MPPI_TRY(ingest_ranges(a.carry_d));
     }
-    h->out_pin_fresh = false;
-    h->results_in_io = true;
-    h->traj_pending = true;  // set before the wait: a failing wait must not leave io_out unguarded for the next call
     stamp(4);
-    MPPI_TRY(waitHostFlag(h, 0, h->io_seq));
-    stamp(5);
-    const float* out = h->io_out_h;
-    std::copy(out, out + (size_t)T * h->C, h->control_h.begin());
-    parseStats(h, out + (h->stats_d - h->out_block_d));
-    h->stats_h_fresh = true;
+    MPPI_TRY(takeControls(h, [&] { stamp(5); }));
     stamp(6);
     if (!allFinite(h->control_h))
       return fail(h, MPPI_ERR_NAN, "mppi_compute_control: non-finite value in the control sequence");
@@ -370,27 +392,22 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
   }
   // one hand-over in (x0, nominal control, control history), one back (control, state and output trajectories, stats):
   // two copies through pinned memory and a single synchronisation per call
-  float* in = h->in_pin_h;
-  std::copy(x0, x0 + h->S, in + (h->x0_d - h->in_block_d));
-  std::copy(h->control_h.begin(), h->control_h.end(), in + (h->mean_d - h->in_block_d));
-  std::copy(h->history_h.begin(), h->history_h.end(), in + (h->history_d - h->in_block_d));
-  HIP_TRY(h, hipMemcpyAsync(h->in_block_d, in, sizeof(float) * h->in_floats, hipMemcpyHostToDevice, h->stream));
+  stageInputs(h, h->in_pin_h, x0, h->sys.control, h->sys.history, 0);
+  HIP_TRY(h, hipMemcpyAsync(h->in_block_d, h->in_pin_h, sizeof(float) * h->in_floats, hipMemcpyHostToDevice, h->stream));
   for (int it = 0; it < h->cfg.num_iters; it++)
     MPPI_TRY(iteration(h, it, stride));
   MPPI_TRY(flushMerge(h));  // the last iteration's records (streamed merge): everything below reads mean_d / stats_d
-  a.control_out_d = h->ctrl_out_d;
-  a.state_out_d = h->state_out_d;
-  a.output_out_d = h->output_out_d;
+  std::string err;
   const mppi_status st = h->model->launchFinalize(1, a, h->stream, err);
   if (st != MPPI_OK)
     return fail(h, st, err);
   HIP_TRY(h, hipMemcpyAsync(h->out_pin_h, h->out_block_d, sizeof(float) * h->out_floats, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  const float* out = h->out_pin_h;
-  std::copy(out, out + (size_t)T * h->C, h->control_h.begin());
-  std::copy(out + (h->state_out_d - h->out_block_d), out + (h->state_out_d - h->out_block_d) + (size_t)T * h->S,
-            h->state_h.begin());
-  parseStats(h, out + (h->stats_d - h->out_block_d));
+  const float* u = outSlice(h->out_pin_h, h->out.control);
+  const float* xs = outSlice(h->out_pin_h, h->out.state);
+  std::copy(u, u + (size_t)T * h->C, h->control_h.begin());
+  std::copy(xs, xs + (size_t)T * h->S, h->state_h.begin());
+  parseStats(h, outSlice(h->out_pin_h, h->out.stats));
   h->out_pin_fresh = true;
   h->results_in_io = false;
   // base_plant.hpp:515-528 checks both the control and the state trajectory
@@ -412,95 +429,12 @@ static mppi_status computeControlTube(mppi_handle h, const float* x0, int stride
   if (h->low_latency)
   {
     /* Inputs and results through host memory mapped into the device, flags instead of copies + synchronisations (see
-     * computeControlVanilla).  Every optimisation pass needs both trajectories on the host (the nominal system is replaced by
-     * the actual one when that is the better of the two, :264-277), so the loop waits for all four flags; the final smoothing
-     * pass returns with the control sequences and leaves its two trajectories to ensureTrajectories(). */
+     * computeControlVanilla): the call returns with both control sequences and leaves the two trajectories to
+     * ensureTrajectories(). */
     // (split hand-over: nothing of this call touches what the last call's trajectory phase reads or writes — see
     // computeControlVanilla — and the nominal system's state is tube_x_h, not row 0 of a trajectory still on its way)
     if (!h->split_finalize)
       MPPI_TRY(ensureTrajectories(h));
-    const int T = h->cfg.num_timesteps;
-    auto stage_inputs = [&]() -> mppi_status {
-      float* in = h->io_in_h;
-      std::copy(x0, x0 + S, in + (h->x0_d - h->in_block_d));
-      std::copy(h->tube_x_h.begin(), h->tube_x_h.end(), in + (h->x0_d - h->in_block_d) + S);
-      float* mean = in + (h->mean_d - h->in_block_d);
-      std::copy(h->control_h.begin(), h->control_h.end(), mean);
-      std::copy(h->nominal_control_h.begin(), h->nominal_control_h.end(), mean + h->TC);
-      std::copy(h->history_h.begin(), h->history_h.end(), in + (h->history_d - h->in_block_d));
-      launchIngest(h);
-      HIP_TRY(h, hipGetLastError());
-      return MPPI_OK;
-    };
-    auto finalize_flagged = [&](const int smooth_mask) -> mppi_status {
-      kernels::FinalizeArgs a{};
-  a.scratch_d = h->fin_scratch_d;
-      a.control_in_d = h->mean_d;
-      a.history_d = h->history_d;
-      a.history_stride = 0;
-      a.x0_d = h->x0_d;
-      a.dt = h->cfg.dt;
-      a.num_timesteps = T;
-      a.smooth_mask = smooth_mask;
-      a.constrain_mask = 0;
-      a.constrain_mode = 0;
-      a.control_out_d = h->io_out_h.dev() + (h->ctrl_out_d - h->out_block_d);
-      a.state_out_d = h->io_out_h.dev() + (h->state_out_d - h->out_block_d);
-      a.output_out_d = h->io_out_h.dev() + (h->output_out_d - h->out_block_d);
-      a.stats_in_d = h->stats_d;
-      a.stats_out_d = h->io_out_h.dev() + (h->stats_d - h->out_block_d);
-      a.stats_floats = 2 * kernels::STATS_STRIDE;
-      a.flags_d = h->io_flags_h.dev();
-      a.seq = ++h->io_seq;
-      std::string err;
-      float* carry = nullptr;
-      if (h->split_finalize)
-      {  // as computeControlVanilla: control phase here, both systems' re-rollouts on the side stream from the carry block
-        const unsigned p = a.seq & 1u;
-        if (h->carry_seq[p] != 0)
-        {
-          MPPI_TRY(waitHostFlagReached(h, 1, h->carry_seq[p]));
-          MPPI_TRY(waitHostFlagReached(h, 3, h->carry_seq[p]));
-        }
-        carry = h->carry_d + (size_t)p * h->in_floats;
-        a.phases = 1;
-        a.carry_d = carry;
-        a.carry_src_d = h->in_block_d;  // (ingested; tubeSelectKernel has put the chosen nominal state and control there)
-        a.carry_floats = (int)h->in_floats;
-        a.carry_mean_off = (int)(h->mean_d - h->in_block_d);
-        a.carry_ready_d = reinterpret_cast<unsigned*>(h->carry_d + 2 * h->in_floats) + 2 * p;
-      }
-      const mppi_status st = h->model->launchFinalize(2, a, h->stream, err);
-      if (st != MPPI_OK)
-        return fail(h, st, err);
-      if (h->split_finalize)
-      {
-        kernels::FinalizeArgs b = a;
-        b.phases = 2;
-        b.carry_d = nullptr;
-        b.control_in_d = carry + (h->mean_d - h->in_block_d);
-        b.x0_d = carry + (h->x0_d - h->in_block_d);
-        b.smooth_mask = 0;
-        b.scratch_d = h->fin_scratch2_d;
-        const mppi_status st2 = h->model->launchFinalize(2, b, h->side_stream, err);
-        if (st2 != MPPI_OK)
-          return fail(h, st2, err);
-        HIP_TRY(h, hipEventRecord(h->ev_side, h->side_stream));
-        h->side_pending = true;
-        h->carry_seq[a.seq & 1u] = a.seq;
-      }
-      h->out_pin_fresh = false;
-      h->results_in_io = true;
-      h->traj_pending = true;  // set before the waits: a failing wait must not leave io_out unguarded for the next call
-      MPPI_TRY(waitHostFlag(h, 0, h->io_seq));
-      MPPI_TRY(waitHostFlag(h, 2, h->io_seq));
-      const float* out = h->io_out_h;
-      std::copy(out, out + (size_t)T * h->C, h->control_h.begin());
-      std::copy(out + (size_t)T * h->C, out + (size_t)2 * T * h->C, h->nominal_control_h.begin());
-      parseStats(h, out + (h->stats_d - h->out_block_d));
-      h->stats_h_fresh = true;
-      return MPPI_OK;
-    };
     /* Round 5: ONE hand-over per call.  Between two optimisation passes the reference decides on the host whether the nominal
      * system restarts from the actual one (:264-277) — after computing both state trajectories, of which the decision needs
      * nothing and the next pass only row 0, the initial state.  Rounds 2-4 mirrored that: finalize pass, wait for both
@@ -508,7 +442,9 @@ static mppi_status computeControlTube(mppi_handle h, const float* x0, int stride
      * baselines the merge has just written: tubeSelectKernel takes it on the device (nominal mean and initial state
      * overwritten where the actual system wins), the passes chain without the host, and a single finalize pass — smoothing the
      * nominal control, re-rolling both trajectories — hands everything over.  Same values in every host-visible field. */
-    MPPI_TRY(stage_inputs());
+    stageInputs(h, h->io_in_h, x0, h->sys.control, h->sys.history, 0);
+    launchIngest(h);
+    HIP_TRY(h, hipGetLastError());
     for (int it = 0; it < h->cfg.num_iters; it++)
     {
       MPPI_TRY(iteration(h, it, stride));
@@ -516,11 +452,16 @@ static mppi_status computeControlTube(mppi_handle h, const float* x0, int stride
                          h->nominal_threshold);
       HIP_TRY(h, hipGetLastError());
     }
-    // smoothControlTrajectory() smooths the nominal control (:281, :325-329), then computeStateTrajectory(state)
-    MPPI_TRY(finalize_flagged(/*smooth nominal*/ 2));
+    // smoothControlTrajectory() smooths the nominal control (:281, :325-329), then computeStateTrajectory(state).  Split hand-over
+    // as in computeControlVanilla: both systems' re-rollouts on the side stream, from the carry block — a copy of the ingested
+    // input block, where tubeSelectKernel has put the chosen nominal state and control
+    kernels::FinalizeArgs a = finalizeArgs(h, h->mean_d, 0, /*smooth nominal*/ 2, 0);
+    toOutbox(h, a, 2);
+    MPPI_TRY(launchHandover(h, a, 2, h->in_block_d, nullptr));
+    MPPI_TRY(takeControls(h, [] {}));
     if (h->cfg.num_iters > 0)
     {
-      const float* st1 = h->io_out_h + (h->stats_d - h->out_block_d) + kernels::STATS_STRIDE;
+      const float* st1 = outSlice(h->io_out_h, h->out.stats) + kernels::STATS_STRIDE;
       // tubeSelectKernel: bit 0 = the LAST pass kept the nominal system (nominalStateUsed), bit 1 = the nominal system's initial
       // state on the device is the actual one — after a take-over in ANY pass of this call (the reference's
       // nominal_state_trajectory_ persists across the passes, tube_mppi_controller.cu:268-277), not only in the last
@@ -533,14 +474,12 @@ static mppi_status computeControlTube(mppi_handle h, const float* x0, int stride
       return fail(h, MPPI_ERR_NAN, "mppi_compute_control: non-finite value in the control sequence");
     return MPPI_OK;
   }
-  std::vector<float>* co[2] = { &h->control_h, &h->nominal_control_h };
-  std::vector<float>* so[2] = { &h->state_h, &h->nominal_state_h };
   for (int it = 0; it < h->cfg.num_iters; it++)
   {
     MPPI_TRY(uploadTube(h, x0));
     MPPI_TRY(iteration(h, it, stride));
     // new means -> host control_ / nominal_control_trajectory_, then both state trajectories (:255-263)
-    MPPI_TRY(finalize(h, h->mean_d, 0, 0, co, so));
+    MPPI_TRY(finalize(h, h->mean_d, 0, 0, h->sys.control, h->sys.state));
     MPPI_TRY(fetchStats(h));
     if (h->stats_h.real_sys.baseline < h->stats_h.nominal_sys.baseline + h->nominal_threshold)
     {
@@ -559,7 +498,7 @@ static mppi_status computeControlTube(mppi_handle h, const float* x0, int stride
   HIP_TRY(h, hipMemcpyAsync(h->ctrl_in_d + h->TC, h->nominal_control_h.data(), sizeof(float) * h->TC,
                             hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(h->x0_d + S, h->tube_x_h.data(), sizeof(float) * S, hipMemcpyHostToDevice, h->stream));
-  MPPI_TRY(finalize(h, h->ctrl_in_d, /*smooth nominal*/ 2, 0, co, so));
+  MPPI_TRY(finalize(h, h->ctrl_in_d, /*smooth nominal*/ 2, 0, h->sys.control, h->sys.state));
   if (!allFinite(h->control_h) || !allFinite(h->nominal_control_h) || !allFinite(h->state_h) ||
       !allFinite(h->nominal_state_h))
     return fail(h, MPPI_ERR_NAN, "mppi_compute_control: non-finite value in the control or state sequence");
@@ -643,28 +582,12 @@ static mppi_status rmNominalStateTrajectory(mppi_handle h)
   if (h->low_latency)
   {
     // inputs with the input block, the trajectory back through the device-mapped output block + flag (system 0 only)
-    const int T = h->cfg.num_timesteps;
-    float* in = h->io_in_h;
-    std::copy(h->rm_nominal_state.begin(), h->rm_nominal_state.begin() + h->S, in + (h->x0_d - h->in_block_d));
-    std::copy(h->nominal_control_h.begin(), h->nominal_control_h.end(), in + (h->mean_d - h->in_block_d));
+    std::copy(h->rm_nominal_state.begin(), h->rm_nominal_state.end(), inSlice(h->io_in_h, h->in.x0));
+    std::copy(h->nominal_control_h.begin(), h->nominal_control_h.end(), inSlice(h->io_in_h, h->in.mean));
     launchIngest(h);
     HIP_TRY(h, hipGetLastError());
-    kernels::FinalizeArgs a{};
-    a.scratch_d = h->fin_scratch_d;
-    a.control_in_d = h->mean_d;
-    a.history_d = h->history_d;
-    a.history_stride = 0;
-    a.x0_d = h->x0_d;
-    a.dt = h->cfg.dt;
-    a.num_timesteps = T;
-    a.smooth_mask = 0;
-    a.constrain_mask = 0;
-    a.constrain_mode = 0;
-    a.control_out_d = h->io_out_h.dev() + (h->ctrl_out_d - h->out_block_d);
-    a.state_out_d = h->io_out_h.dev() + (h->state_out_d - h->out_block_d);
-    a.output_out_d = h->io_out_h.dev() + (h->output_out_d - h->out_block_d);
-    a.flags_d = h->io_flags_h.dev();
-    a.seq = ++h->io_seq;
+    kernels::FinalizeArgs a = finalizeArgs(h, h->mean_d, 0, 0, 0);
+    toOutbox(h, a, /*no statistics*/ 0);
     std::string err;
     const mppi_status st = h->model->launchFinalize(1, a, h->stream, err);
     if (st != MPPI_OK)
@@ -672,16 +595,14 @@ static mppi_status rmNominalStateTrajectory(mppi_handle h)
     h->out_pin_fresh = false;
     h->results_in_io = true;
     MPPI_TRY(waitHostFlag(h, 1, h->io_seq));
-    const float* xs = h->io_out_h + (h->state_out_d - h->out_block_d);
-    std::copy(xs, xs + (size_t)T * h->S, h->nominal_state_h.begin());
+    const float* xs = outSlice(h->io_out_h, h->out.state);
+    std::copy(xs, xs + h->nominal_state_h.size(), h->nominal_state_h.begin());
     return MPPI_OK;
   }
   HIP_TRY(h, hipMemcpyAsync(h->x0_d, h->rm_nominal_state.data(), sizeof(float) * h->S, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(h->ctrl_in_d, h->nominal_control_h.data(), sizeof(float) * h->TC, hipMemcpyHostToDevice,
                             h->stream));
-  std::vector<float>* co[2] = { nullptr, nullptr };
-  std::vector<float>* so[2] = { &h->nominal_state_h, nullptr };
-  return finalize(h, h->ctrl_in_d, 0, 0, co, so, 1);
+  return finalize(h, h->ctrl_in_d, 0, 0, nullptr, h->sys.state, /*the nominal system alone*/ 1);
 }
 
 /** reference: robust_mppi_controller.cu:571-626 (computeNominalStateAndStride) */
@@ -719,7 +640,7 @@ static mppi_status rmNominalStateAndStride(mppi_handle h, const float* state, in
     // nominal control goes up with the input block: no copy command
     std::copy(h->rm_cand_states.begin(), h->rm_cand_states.end(), h->cand_io_h.get());
     std::memcpy(h->cand_io_h + (size_t)nc * S, h->rm_cand_strides.data(), sizeof(int) * nc);
-    std::copy(h->nominal_control_h.begin(), h->nominal_control_h.end(), h->io_in_h + (h->mean_d - h->in_block_d));
+    std::copy(h->nominal_control_h.begin(), h->nominal_control_h.end(), inSlice(h->io_in_h, h->in.mean));
     launchIngest(h);
     HIP_TRY(h, hipGetLastError());
     cand_costs_dev = h->cand_io_h.dev() + (size_t)nc * (S + 1);
@@ -814,20 +735,14 @@ static mppi_status rmNominalStateAndStride(mppi_handle h, const float* state, in
     HIP_TRY(h, hipGetLastError());
   }
   h->rm_cand_costs.resize((size_t)nc * ns);
-  if (h->low_latency)
-  {
-    const unsigned seq = ++h->cand_seq;
-    hipLaunchKernelGGL(kernels::raiseFlagKernel, dim3(1), dim3(64), 0, h->stream, h->io_flags_h.dev() + 9, seq);
-    HIP_TRY(h, hipGetLastError());
-    MPPI_TRY(waitHostFlag(h, 9, seq));
-    const float* costs = h->cand_io_h + (size_t)nc * (S + 1);
-    std::copy(costs, costs + (size_t)nc * ns, h->rm_cand_costs.begin());
-  }
-  else
-  {
+  if (!h->low_latency)
     HIP_TRY(h, hipMemcpyAsync(h->rm_cand_costs.data(), h->cand_costs_d, sizeof(float) * nc * ns, hipMemcpyDeviceToHost,
                               h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+  MPPI_TRY(streamRoundTrip(h, 9, h->cand_seq));
+  if (h->low_latency)
+  {  // (the kernel wrote them in place)
+    const float* costs = h->cand_io_h + (size_t)nc * (S + 1);
+    std::copy(costs, costs + (size_t)nc * ns, h->rm_cand_costs.begin());
   }
   if (shard_eval)
     for (float c : h->rm_cand_costs)
@@ -863,15 +778,9 @@ static mppi_status computeControlRobust(mppi_handle h, const float* x0_real, int
      * rmNominalStateAndStride and the trajectory getters wait for it).  AutoRally-NN, T = 150: 179 us of a 622 us call. */
     if (h->traj_pending)
       MPPI_TRY(ensureTrajectories(h));
-    float* in = h->io_in_h;
-    std::copy(h->rm_nominal_state.begin(), h->rm_nominal_state.begin() + S, in + (h->x0_d - h->in_block_d));
-    std::copy(x0_real, x0_real + S, in + (h->x0_d - h->in_block_d) + S);
-    float* mean = in + (h->mean_d - h->in_block_d);
-    std::copy(h->nominal_control_h.begin(), h->nominal_control_h.end(), mean);
-    std::copy(h->nominal_control_h.begin(), h->nominal_control_h.end(), mean + h->TC);
-    float* hist = in + (h->history_d - h->in_block_d);
-    std::copy(h->nominal_history_h.begin(), h->nominal_history_h.end(), hist);
-    std::copy(h->history_h.begin(), h->history_h.end(), hist + 2 * h->C);
+    // both importance samplers start from the nominal control (:655-656), each system smooths with its own history
+    const std::vector<float>* const means[2] = { &h->nominal_control_h, &h->nominal_control_h };
+    stageInputs(h, h->io_in_h, x0_real, means, h->sys.history, 2 * h->C);
     launchIngest(h);
     HIP_TRY(h, hipGetLastError());
     for (int it = 0; it < h->cfg.num_iters; it++)
@@ -880,40 +789,11 @@ static mppi_status computeControlRobust(mppi_handle h, const float* x0_real, int
         HIP_TRY(h, hipMemcpyAsync(h->mean_d + h->TC, h->mean_d, sizeof(float) * h->TC, hipMemcpyDeviceToDevice, h->stream));
       MPPI_TRY(iteration(h, it, stride));
     }
-    const int T = h->cfg.num_timesteps;
-    kernels::FinalizeArgs a{};
-  a.scratch_d = h->fin_scratch_d;
-    a.control_in_d = h->mean_d;
-    a.history_d = h->history_d;
-    a.history_stride = 2 * h->C;
-    a.x0_d = h->x0_d;
-    a.dt = h->cfg.dt;
-    a.num_timesteps = T;
-    a.smooth_mask = 3;
-    a.constrain_mask = 0;
-    a.constrain_mode = 0;
-    a.control_out_d = h->io_out_h.dev() + (h->ctrl_out_d - h->out_block_d);
-    a.state_out_d = h->io_out_h.dev() + (h->state_out_d - h->out_block_d);
-    a.output_out_d = h->io_out_h.dev() + (h->output_out_d - h->out_block_d);
-    a.stats_in_d = h->stats_d;
-    a.stats_out_d = h->io_out_h.dev() + (h->stats_d - h->out_block_d);
-    a.stats_floats = 2 * kernels::STATS_STRIDE;
-    a.flags_d = h->io_flags_h.dev();
-    a.seq = ++h->io_seq;
-    std::string err;
-    const mppi_status st = h->model->launchFinalize(2, a, h->stream, err);
-    if (st != MPPI_OK)
-      return fail(h, st, err);
-    h->out_pin_fresh = false;
-    h->results_in_io = true;
-    h->traj_pending = true;  // set before the waits: a failing wait must not leave io_out unguarded for the next call
-    MPPI_TRY(waitHostFlag(h, 0, h->io_seq));
-    MPPI_TRY(waitHostFlag(h, 2, h->io_seq));
-    const float* out = h->io_out_h;
-    std::copy(out, out + (size_t)T * h->C, h->nominal_control_h.begin());
-    std::copy(out + (size_t)T * h->C, out + (size_t)2 * T * h->C, h->control_h.begin());
-    parseStats(h, out + (h->stats_d - h->out_block_d));
-    h->stats_h_fresh = true;
+    // smooth both with their own history, then both state trajectories (:732-737); one launch (no split for this controller)
+    kernels::FinalizeArgs a = finalizeArgs(h, h->mean_d, 2 * h->C, /*smooth both*/ 3, 0);
+    toOutbox(h, a, 2);
+    MPPI_TRY(launchHandover(h, a, 2, nullptr, nullptr));
+    MPPI_TRY(takeControls(h, [] {}));
     if (!allFinite(h->control_h) || !allFinite(h->nominal_control_h))
       return fail(h, MPPI_ERR_NAN, "mppi_compute_control: non-finite value in the control sequence");
     return MPPI_OK;
@@ -924,9 +804,7 @@ static mppi_status computeControlRobust(mppi_handle h, const float* x0_real, int
     MPPI_TRY(iteration(h, it, stride));
   }
   // smooth both with their own history, then the nominal state trajectory from the smoothed nominal control (:732-737)
-  std::vector<float>* co[2] = { &h->nominal_control_h, &h->control_h };
-  std::vector<float>* so[2] = { &h->nominal_state_h, &h->state_h };
-  MPPI_TRY(finalize(h, h->mean_d, /*smooth both*/ 3, /*constrain*/ 0, co, so));
+  MPPI_TRY(finalize(h, h->mean_d, /*smooth both*/ 3, /*constrain*/ 0, h->sys.control, h->sys.state));
   MPPI_TRY(fetchStats(h));
   if (!allFinite(h->control_h) || !allFinite(h->nominal_control_h) || !allFinite(h->nominal_state_h))
     return fail(h, MPPI_ERR_NAN, "mppi_compute_control: non-finite value in the control or state sequence");
@@ -965,8 +843,8 @@ mppi_status mppi_get_state_seq(mppi_handle h, float* x)
   if (!x)
     return fail(h, MPPI_ERR_INVALID_ARG, "null");
   MPPI_TRY(ensureTrajectories(h));
-  // RobustMPPI::getTargetStateSeq returns the nominal state trajectory (robust_mppi_controller.cuh:131-134)
-  const std::vector<float>& src = h->cfg.controller == MPPI_CONTROLLER_ROBUST ? h->nominal_state_h : h->state_h;
+  // system 0: RobustMPPI::getTargetStateSeq returns the nominal state trajectory (robust_mppi_controller.cuh:131-134)
+  const std::vector<float>& src = *h->sys.state[0];
   std::copy(src.begin(), src.end(), x);
   return MPPI_OK;
 }
@@ -980,7 +858,7 @@ mppi_status mppi_get_output_seq(mppi_handle h, float* y)
   if (h->results_in_io)
   {  // the last finalize pass wrote its outputs to the device-mapped host block
     MPPI_TRY(ensureTrajectories(h));
-    const float* src = h->io_out_h + (h->output_out_d - h->out_block_d);
+    const float* src = outSlice(h->io_out_h, h->out.output);
     std::copy(src, src + (size_t)h->cfg.num_timesteps * h->O, y);
     return MPPI_OK;
   }
@@ -1013,11 +891,6 @@ mppi_status mppi_get_nominal_state_seq(mppi_handle h, float* x)
   std::copy(h->nominal_state_h.begin(), h->nominal_state_h.end(), x);
   return MPPI_OK;
 }
-
-static void saveControlHistory(int steps, const std::vector<float>& u, std::vector<float>& hist, int C);
-static void slideSequence(std::vector<float>& u, int T, int C, int steps, const float* zero, const float* scale);
-static mppi_status rmNominalStateAndStride(mppi_handle h, const float* state, int stride);
-static mppi_status rmNominalStateTrajectory(mppi_handle h);
 
 /** reference: controllers/controller.cuh:602-615 */
 static void saveControlHistory(int steps, const std::vector<float>& u, std::vector<float>& hist, int C)
@@ -1064,17 +937,7 @@ mppi_status modelStepInPlace(mppi_handle h, float* x, float* u, float dt, int en
   mppi_status st = h->model->launchModelStep(h->step_pin_h.dev(), h->step_pin_h.dev() + h->S, dt, enforce, h->stream, err);
   if (st != MPPI_OK)
     return fail(h, st, err);
-  if (h->low_latency)
-  {
-    const unsigned seq = ++h->step_seq;
-    hipLaunchKernelGGL(kernels::raiseFlagKernel, dim3(1), dim3(64), 0, h->stream, h->io_flags_h.dev() + 8, seq);
-    HIP_TRY(h, hipGetLastError());
-    MPPI_TRY(waitHostFlag(h, 8, seq));
-  }
-  else
-  {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  }
+  MPPI_TRY(streamRoundTrip(h, 8, h->step_seq));
   std::copy(h->step_pin_h.get(), h->step_pin_h + h->S, x);
   std::copy(h->step_pin_h + h->S, h->step_pin_h + h->S + h->C, u);
   return MPPI_OK;

@@ -78,6 +78,29 @@ inline ModelBase* makeModel(const std::string& name, int sampler_kind)
   return f ? static_cast<ModelBase*>(f()) : nullptr;
 }
 
+/** where a slice starts in the input block (x0 | mean | history) / the output block (control | state | output | stats), in floats
+ *  from the block's base.  Fixed at mppi_create; the same for the device blocks, their pinned and mapped mirrors and the carry
+ *  blocks — inSlice / outSlice below take the base */
+struct InOffset
+{
+  size_t floats = 0;
+};
+struct OutOffset
+{
+  size_t floats = 0;
+};
+
+/** Which host vectors are system z of the kernels (z < D).  Vanilla / Colored: { control_h, state_h }; Tube: { actual, nominal }
+ *  (tube_mppi_controller.cu:255-263); Robust: { nominal, real } (robust_mppi_controller.cu:637-640).  Filled at mppi_create. */
+struct SystemTable
+{
+  std::vector<float>* control[2] = { nullptr, nullptr };
+  std::vector<float>* state[2] = { nullptr, nullptr };
+  const std::vector<float>* history[2] = { nullptr, nullptr };  // [1] only where system 1 smooths with a history of its own
+  const std::vector<float>* x0[2] = { nullptr, nullptr };       // nullptr: the state the caller of mppi_compute_control measured
+  mppi_system_stats* stats[2] = { nullptr, nullptr };
+};
+
 struct mppi_handle_s
 {
   /* Entry points of one handle are serialised: the reference's controllers are single-caller, but its BasePlant calls them
@@ -150,12 +173,21 @@ struct mppi_handle_s
    * results back with one copy and one synchronisation (single-system controllers; the others copy slice by slice) */
   HipBuffer<float> in_block_d;
   HipBuffer<float> out_block_d;
+  struct
+  {
+    InOffset x0, mean, history;
+  } in;
+  struct
+  {
+    OutOffset control, state, output, stats;
+  } out;
+  SystemTable sys;
   HipBuffer<float> in_pin_h;
   HipBuffer<float> out_pin_h;
-  /* low-latency hand-over of the single-system controllers (computeControlVanilla): host memory mapped into the device —
-   * the first kernel reads the inputs from io_in, the finalize kernel writes the results to io_out and raises io_flags the
-   * host spins on (flag 0: control sequence + statistics out; flag 1: state / output trajectories out); .dev() is the
-   * device address of each */
+  /* low-latency hand-over of all four computeControl loops: host memory mapped into the device — the first kernel reads the
+   * inputs from io_in, the finalize kernel writes the results to io_out and raises io_flags the host spins on (flag 0: control
+   * sequence + statistics out; flag 1: state / output trajectories out; flags 2 and 3: the same of a second system); .dev() is
+   * the device address of each */
   HipBuffer<float> io_in_h;
   HipBuffer<float> io_out_h;
   HipBuffer<unsigned> io_flags_h;
@@ -307,6 +339,39 @@ inline mppi_status fail(mppi_handle h, mppi_status s, const std::string& msg)
       return s__;                    \
   } while (0)
 
+/** a slice of an input block (`base`: in_block_d, in_pin_h, io_in_h, io_in_h.dev(), a carry block) / of an output block
+ *  (out_block_d, out_pin_h, io_out_h, io_out_h.dev()) */
+static inline float* inSlice(float* base, InOffset slice)
+{
+  return base + slice.floats;
+}
+static inline float* outSlice(float* base, OutOffset slice)
+{
+  return base + slice.floats;
+}
+
+/** what every finalize pass starts from: inputs and results in the device blocks, smoothing / constraint masks per system (bit z) */
+static inline kernels::FinalizeArgs finalizeArgs(mppi_handle h, const float* control_in_d, int history_stride, int smooth_mask,
+                                                 int constrain_mask)
+{
+  kernels::FinalizeArgs a{};
+  a.scratch_d = h->fin_scratch_d;
+  a.control_in_d = control_in_d;
+  a.history_d = h->history_d;
+  a.history_stride = history_stride;
+  a.x0_d = h->x0_d;
+  a.control_out_d = h->ctrl_out_d;
+  a.state_out_d = h->state_out_d;
+  a.output_out_d = h->output_out_d;
+  a.dt = h->cfg.dt;
+  a.num_timesteps = h->cfg.num_timesteps;
+  a.smooth_mask = smooth_mask;
+  a.constrain_mask = constrain_mask;
+  // ColoredMPPI clamps only control channel 1 after smoothing (colored_mppi_controller.cu:232-237)
+  a.constrain_mode = h->cfg.controller == MPPI_CONTROLLER_COLORED ? 1 : 0;
+  return a;
+}
+
 /** split hand-over: order the handle's stream behind the trajectory phase that may still run on the side stream — whatever an
  *  entry point enqueues or synchronises on h->stream then sees the state a single in-order stream would have given it */
 static inline void joinSideStream(mppi_handle h)
@@ -433,7 +498,7 @@ MPPI_ENGINE_INTERNAL mppi_status iteration(mppi_handle h, int it, int stride);
 MPPI_ENGINE_INTERNAL mppi_status fetchStats(mppi_handle h);
 MPPI_ENGINE_INTERNAL bool allFinite(const std::vector<float>& v);
 MPPI_ENGINE_INTERNAL mppi_status finalize(mppi_handle h, const float* ctrl_in_d, int smooth_mask, int constrain_mask,
-                            std::vector<float>* ctrl_out[2], std::vector<float>* state_out[2], int num_systems = 0);
+                            std::vector<float>* const ctrl_out[2], std::vector<float>* const state_out[2], int num_systems = 0);
 MPPI_ENGINE_INTERNAL void parseStats(mppi_handle h, const float* st);
 MPPI_ENGINE_INTERNAL mppi_status modelStepInPlace(mppi_handle h, float* x, float* u, float dt, int enforce);
 

@@ -389,7 +389,7 @@ mppi_status fetchStats(mppi_handle h)
     return MPPI_OK;
   if (h->out_pin_fresh)
   {  // the last finalize pass brought the statistics along
-    parseStats(h, h->out_pin_h + (h->stats_d - h->out_block_d));
+    parseStats(h, outSlice(h->out_pin_h, h->out.stats));
     return MPPI_OK;
   }
   float st[2 * kernels::STATS_STRIDE] = { 0 };
@@ -408,40 +408,22 @@ bool allFinite(const std::vector<float>& v)
   return true;
 }
 
-/** smoothing / state trajectories / constraints for the D systems in ctrl_in_d, results to the host vectors */
+/** smoothing / state trajectories / constraints for the D systems in ctrl_in_d, results to the host vectors (a null table, or a
+ *  null entry: that sequence stays where it is) */
 mppi_status finalize(mppi_handle h, const float* ctrl_in_d, int smooth_mask, int constrain_mask,
-                            std::vector<float>* ctrl_out[2], std::vector<float>* state_out[2], int num_systems)
+                            std::vector<float>* const ctrl_out[2], std::vector<float>* const state_out[2], int num_systems)
 {
   RoctxRange range("mppi:finalize");
   const int T = h->cfg.num_timesteps;
-  kernels::FinalizeArgs a{};
-  a.scratch_d = h->fin_scratch_d;
-  // the control history goes up through its slice of the pinned input block (one small asynchronous copy)
-  float* hist_pin = h->in_pin_h + (h->history_d - h->in_block_d);
-  if (h->cfg.controller == MPPI_CONTROLLER_ROBUST)
-  {  // system 0 (nominal) smooths with nominal_control_history_, system 1 (real) with control_history_
-    std::copy(h->nominal_history_h.begin(), h->nominal_history_h.end(), hist_pin);
-    std::copy(h->history_h.begin(), h->history_h.end(), hist_pin + 2 * h->C);
-    a.history_stride = 2 * h->C;
-  }
-  else
-  {
-    std::copy(h->history_h.begin(), h->history_h.end(), hist_pin);
-    a.history_stride = 0;
-  }
+  // the control history goes up through its slice of the pinned input block (one small asynchronous copy); Robust MPPI: system 0
+  // (nominal) smooths with nominal_control_history_, system 1 (real) with control_history_
+  const int history_stride = h->sys.history[1] ? 2 * h->C : 0;
+  float* hist_pin = inSlice(h->in_pin_h, h->in.history);
+  for (int z = 0; z < 2; z++)
+    if (h->sys.history[z])
+      std::copy(h->sys.history[z]->begin(), h->sys.history[z]->end(), hist_pin + z * history_stride);
   HIP_TRY(h, hipMemcpyAsync(h->history_d, hist_pin, sizeof(float) * 4 * h->C, hipMemcpyHostToDevice, h->stream));
-  a.control_in_d = ctrl_in_d;
-  a.history_d = h->history_d;
-  a.x0_d = h->x0_d;
-  a.control_out_d = h->ctrl_out_d;
-  a.state_out_d = h->state_out_d;
-  a.output_out_d = h->output_out_d;
-  a.dt = h->cfg.dt;
-  a.num_timesteps = T;
-  a.smooth_mask = smooth_mask;
-  a.constrain_mask = constrain_mask;
-  // ColoredMPPI clamps only control channel 1 after smoothing (colored_mppi_controller.cu:232-237)
-  a.constrain_mode = h->cfg.controller == MPPI_CONTROLLER_COLORED ? 1 : 0;
+  const kernels::FinalizeArgs a = finalizeArgs(h, ctrl_in_d, history_stride, smooth_mask, constrain_mask);
   std::string err;
   const int nsys = num_systems > 0 ? num_systems : h->D;
   mppi_status st = h->model->launchFinalize(nsys, a, h->stream, err);
@@ -453,11 +435,11 @@ mppi_status finalize(mppi_handle h, const float* ctrl_in_d, int smooth_mask, int
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   for (int z = 0; z < nsys; z++)
   {
-    const float* c = h->out_pin_h + (h->ctrl_out_d - h->out_block_d) + (size_t)z * T * h->C;
-    const float* x = h->out_pin_h + (h->state_out_d - h->out_block_d) + (size_t)z * T * h->S;
-    if (ctrl_out[z])
+    const float* c = outSlice(h->out_pin_h, h->out.control) + (size_t)z * T * h->C;
+    const float* x = outSlice(h->out_pin_h, h->out.state) + (size_t)z * T * h->S;
+    if (ctrl_out && ctrl_out[z])
       std::copy(c, c + (size_t)T * h->C, ctrl_out[z]->begin());
-    if (state_out[z])
+    if (state_out && state_out[z])
       std::copy(x, x + (size_t)T * h->S, state_out[z]->begin());
   }
   h->out_pin_fresh = true;
