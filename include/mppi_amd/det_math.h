@@ -18,7 +18,7 @@
  * explicit det::fma() calls (hipcc: v_fma_f32; gcc -mfma: vfmadd, or glibc's correctly rounded fmaf()).
  * Result: identical bits on the MI355X and on the host, which tests/test_det_math.py checks on the GPU.
  *
- * Accuracy (checked against float64 libm in tests/test_det_math.py): sin/cos/exp/log <= 2 ulp, atan <= 3 ulp, tanh
+ * Accuracy (checked against float64 libm in tests/test_det_math.py): sin/cos/exp/log <= 2 ulp, atan and atan2 <= 3 ulp, tanh
  * <= 7 ulp (4e-7 absolute; branch-free rational form) on the ranges the models use.  That is tighter than the reference's own device intrinsics, and well inside the
  * reference's GPU-vs-CPU test tolerances (tests/mppi_core/rollout_kernel_tests.cu:258: 1e-4 relative).
  *
@@ -671,6 +671,63 @@ MPPI_HD static inline float asin(float x)
   y = copysign(y, x);
   y = (a < 1.0e-4f) ? x : y;  // selects, not early returns: no divergent branch in a rollout step
   return (a <= 1.0f) ? y : u2f(0x7fc00000u);
+}
+
+/** atan2(y, x) with det::atan's range reduction and polynomial applied to the pair itself: the reduced argument is
+ *  -|x| / |y|, (|y| - |x|) / (|y| + |x|) or |y| / |x| — one true division, no quotient rounded before it is reduced — added to
+ *  pi/2, pi/4 or 0; for x < 0 it is subtracted from the supplement of that base, held in two parts; the result takes the sign of y.
+ *  Zeros and axes as libm: atan2(+-0, x >= +0) = +-0, atan2(+-0, x <= -0) = +-pi, atan2(y, +-0) = +-pi/2 exactly,
+ *  atan2(+-inf, +-inf) = +-pi/4 or +-3pi/4, NaN in -> NaN out.  Magnitudes above 2^126 are scaled down first (their sum would
+ *  overflow). */
+MPPI_HD static inline float atan2(float y, float x)
+{
+#if defined(MPPI_DET_MATH_LIBM) && !defined(__HIPCC__)
+  return ::atan2f(y, x);
+#endif
+  const float PI_HI = 3.1415927410125732421875f, PI_LO = -8.74227765734758577309548854827880859375e-8f;
+  const float SCALE_ABOVE = 8.507059173023462e37f;  // 2^126
+  float ax = fabs(x), ay = fabs(y);
+  const bool x_neg = (f2u(x) >> 31) != 0u;
+  const bool x_zero = ax == 0.0f, y_zero = ay == 0.0f;
+  if (ax > 3.402823466e38f && ay > 3.402823466e38f)
+    ax = ay = 1.0f;
+  if (ax > SCALE_ABOVE || ay > SCALE_ABOVE)
+  {
+    ax *= 0.0625f;
+    ay *= 0.0625f;
+  }
+  /* base angle of the first quadrant, and for x < 0 its supplement pi - base in two parts */
+  float base, sup_hi, sup_lo, t;
+  if (ay > 2.414213562373095f * ax)
+  {
+    base = sup_hi = 1.57079637050628662109375f;
+    sup_lo = -4.37113882867379277013e-08f;
+    t = -ax / ay;
+  }
+  else if (ay > 0.4142135623730950f * ax)
+  {
+    base = 0.785398185253143310546875f;
+    sup_hi = 2.35619449615478515625f;
+    sup_lo = -5.962440319251527e-09f;
+    t = (ay - ax) / (ay + ax);
+  }
+  else
+  {
+    base = 0.0f;
+    sup_hi = PI_HI;
+    sup_lo = PI_LO;
+    t = ay / ax;
+  }
+  const float z = t * t;
+  float p = fma(8.05374449538e-2f, z, -1.38776856032e-1f);
+  p = fma(p, z, 1.99777106478e-1f);
+  p = fma(p, z, -3.33329491539e-1f);
+  const float f = fma(p * z, t, t);
+  float a = x_neg ? sup_hi + (sup_lo - f) : base + f;
+  a = x_zero ? 1.57079637050628662109375f : a;
+  a = y_zero ? (x_neg ? PI_HI : 0.0f) : a;
+  a = copysign(a, y);
+  return (x != x || y != y) ? x + y : a;
 }
 
 /** x^y for x > 0 as exp(y*log(x)); used only for slowly varying discount factors (|y*log x| small). */

@@ -12,6 +12,9 @@
  *   mppi_racer_dubins_elevation_params <- RacerDubinsElevationParams dynamics/racer_dubins/racer_dubins_elevation.cuh:16-60
  *   mppi_racer_dubins_suspension_params <- RacerDubinsElevationSuspensionParams dynamics/racer_dubins/racer_dubins_elevation_suspension_lstm.cuh:17-66
  *   mppi_quadratic_cost_params_28   <- QuadraticCostTrajectoryParams<RacerDubins, 1>  cost_functions/quadratic_cost/quadratic_cost.cuh:11-63
+ *   mppi_quadrotor_dynamics_params  <- QuadrotorDynamicsParams       dynamics/quadrotor/quadrotor_dynamics.cuh:10-63
+ *   mppi_quadrotor_cost_params      <- QuadrotorQuadraticCostParams  cost_functions/quadrotor/quadrotor_quadratic_cost.cuh:10-70
+ *                                      (CostParams<4> base; use_euler, the reference's bool, as an int)
  * (paths relative to the reference's include/mppi/).
  */
 #ifndef MPPI_AMD_MODEL_PARAMS_H_
@@ -151,6 +154,30 @@ typedef struct mppi_ar_standard_cost_params
   float r_c2[3];               /* column 2 */
   float trs[3];                /* translation */
 } mppi_ar_standard_cost_params;
+
+typedef struct mppi_quadrotor_dynamics_params
+{
+  float tau_roll;  /* 0.25 s: time constants of the body-rate tracking */
+  float tau_pitch; /* 0.25 */
+  float tau_yaw;   /* 0.25 */
+  float mass;      /* 1.0 kg */
+} mppi_quadrotor_dynamics_params;
+
+typedef struct mppi_quadrotor_cost_params
+{
+  float control_cost_coeff[4]; /* {2, 2, 2, 2} */
+  float discount;              /* 1.0 */
+  float s_goal[13];            /* position, velocity, quaternion (w x y z), body rates: {0,0,0, 0,0,0, 1,0,0,0, 0,0,0} */
+  float x_coeff;               /* 1 */
+  float v_coeff;               /* 1 */
+  int use_euler;               /* 1 (the reference's bool): roll / pitch / yaw of the attitude error, else its quaternion */
+  float q_coeff;               /* 1 */
+  float roll_coeff;            /* 1 */
+  float pitch_coeff;           /* 1 */
+  float yaw_coeff;             /* 1 */
+  float w_coeff;               /* 1 */
+  float terminal_cost_coeff;   /* 0 */
+} mppi_quadrotor_cost_params;
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,35 @@ class DoubleIntegratorCircleCostParams(C.Structure):
         self.angular_momentum_desired = 4
 
 
+class QuadrotorDynamicsParams(C.Structure):
+    """mppi_quadrotor_dynamics_params (reference: dynamics/quadrotor/quadrotor_dynamics.cuh:10-63)"""
+    _fields_ = [("tau_roll", C.c_float), ("tau_pitch", C.c_float), ("tau_yaw", C.c_float), ("mass", C.c_float)]
+
+    def __init__(self, mass=1.0):
+        super().__init__(0.25, 0.25, 0.25, mass)
+
+
+class QuadrotorQuadraticCostParams(C.Structure):
+    """mppi_quadrotor_cost_params (reference: cost_functions/quadrotor/quadrotor_quadratic_cost.cuh:10-70); s_goal is
+    position, velocity, quaternion (w x y z), body rates"""
+    _fields_ = [
+        ("control_cost_coeff", C.c_float * 4), ("discount", C.c_float), ("s_goal", C.c_float * 13),
+        ("x_coeff", C.c_float), ("v_coeff", C.c_float), ("use_euler", C.c_int), ("q_coeff", C.c_float),
+        ("roll_coeff", C.c_float), ("pitch_coeff", C.c_float), ("yaw_coeff", C.c_float), ("w_coeff", C.c_float),
+        ("terminal_cost_coeff", C.c_float),
+    ]
+
+    def __init__(self):
+        super().__init__()
+        self.control_cost_coeff[:] = [2.0] * 4
+        self.discount = 1.0
+        self.s_goal[:] = [0.0] * 6 + [1.0] + [0.0] * 6
+        self.x_coeff = self.v_coeff = self.q_coeff = self.w_coeff = 1.0
+        self.roll_coeff = self.pitch_coeff = self.yaw_coeff = 1.0
+        self.use_euler = 1
+        self.terminal_cost_coeff = 0.0
+
+
 class RacerDubinsParams(C.Structure):
     """mppi_racer_dubins_params (reference: dynamics/racer_dubins/racer_dubins.cuh:67-87)"""
     _fields_ = [("c_t", C.c_float * 3), ("c_b", C.c_float * 3), ("c_v", C.c_float * 3), ("c_0", C.c_float),
@@ -800,6 +829,13 @@ def det_eval(func, x, device=0):
     y = np.empty_like(x)
     _op_check(lib, lib.mppi_det_eval(func, x, y, x.size, device))
     return y
+
+
+def det_atan2(y, x, device=0):
+    """det::atan2 on the device (mppi_det_eval function 14, which takes its arguments as (y, x) pairs)"""
+    y, x = np.broadcast_arrays(_f32(y), _f32(x))
+    pairs = np.stack([y.reshape(-1), x.reshape(-1)], axis=1)
+    return det_eval(14, pairs, device)[0::2].reshape(y.shape)
 
 
 def launch_boundary_us(device=0, n=2000):

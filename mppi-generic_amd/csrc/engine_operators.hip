@@ -258,6 +258,12 @@ __global__ void detEvalKernel(int func, const float* x, float* y, int n)
       }
       case 12: r = mppi::det::tan(x[i]); break;
       case 13: r = mppi::det::asin(x[i]); break;
+      case 14:  // two arguments: x holds (y, x) pairs; both elements of a pair get atan2(y, x), an unpaired last one atan2(y, 1)
+      {
+        const int j = i & ~1;
+        r = mppi::det::atan2(x[j], j + 1 < n ? x[j + 1] : 1.0f);
+        break;
+      }
     }
     y[i] = r;
   }

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Times optimisation iterations of the registered workloads for several block shapes (HIP events on the engine's
-stream).  Usage: python tools/time_workloads.py [cartpole|autorally|di|lstm|racer|nln|nln-gaussian] ...
+stream).  Usage: python tools/time_workloads.py [cartpole|autorally|di|lstm|racer|quadrotor|nln|nln-gaussian] ...
 (nln / nln-gaussian: the Cartpole pipeline kernel at K = 16384, T = 100 with the NLN and with the Gaussian sampler, one workload
-each so that a kernel trace of either holds one rollout kernel; not part of the default set)"""
+each so that a kernel trace of either holds one rollout kernel; not part of the default set.
+quadrotor: the reference's hover configuration at 2048 x 150 and 16384 x 150, each beside the double integrator at the same K and T
+— an analytic model on the same kernels, as the yardstick; not part of the default set either: the model's registration unit is
+examples/quadrotor_model/quadrotor_model.hip, built and loaded here)"""
 import os
 import sys
 
@@ -70,3 +73,13 @@ if "racer" in which:
     cfg = steering_cfg(K=16384, T=100)
     cfg["colored"] = ([1.0, 1.0], 0.97, 0.0)
     run("racer-lstm+colored", cfg, [(0, 0, 0)], n=30)
+if "quadrotor" in which:
+    import mppi_generic_amd as m  # noqa: E402
+    import quadrotor_oracle  # noqa: E402
+    from test_quadrotor import hover_cfg  # noqa: E402
+    quadrotor_oracle.load_model(m)
+    for K in (2048, 16384):
+        cfg = hover_cfg()
+        cfg["K"] = K
+        run("quadrotor", cfg, [(64, 1, 1), (64, 1, 2), (32, 4, 1)], n=50)
+        run("di", di_cfg(K=K, T=150, tube=False), [(64, 1, 1), (64, 1, 2)], n=50)
