@@ -445,6 +445,16 @@ template <class T>
 struct has_costmap<T, std::void_t<decltype(std::declval<T&>().costmap_d_)>> : std::true_type
 {
 };
+template <class T, class = void>
+struct has_cost_texture : std::false_type
+{
+};
+/** a cost with a TwoDTextureHelper member `tex_helper_` (QuadrotorMapCost: the track map); ARStandardCost's costmap_d_ / r_c1
+ *  form is has_costmap, and a class is one or the other (static_assert in ModelT) */
+template <class T>
+struct has_cost_texture<T, std::void_t<decltype(std::declval<T&>().tex_helper_.textures_[0].data)>> : std::true_type
+{
+};
 
 /**
  * DYN_FAST_T / FAST_SHAPES: an optional second Dynamics type implementing the same model for particular block shapes
@@ -915,6 +925,8 @@ struct ModelT : ModelBase
   bool basis_dirty = true;
   HipBuffer<float> weights_d;
   HipBuffer<float> weights2_d;
+  static_assert(!(has_costmap<COST_T>::value && has_cost_texture<COST_T>::value),
+                "a cost class takes its map as costmap_d_ or through a tex_helper_, not both");
   HipBuffer<float> costmap_d;
   HipBuffer<float> elevation_d;
   HipBuffer<float> normals_d;
@@ -1182,6 +1194,42 @@ struct ModelT : ModelBase
         cost.height_ = dims[0];
         cost.width_ = dims[1];
         return st;
+      }
+    }
+    if constexpr (has_cost_texture<COST_T>::value)
+    {
+      /* the cost's TwoDTextureHelper: updateTexture + enableTexture, {height, width} values, row-major; the model runs without it */
+      if (name == "costmap")
+      {
+        if (ndims != 2 || dims[0] <= 0 || dims[1] <= 0 || (size_t)dims[0] * dims[1] != count)
+        {
+          err = "costmap: dims must be {height, width} with height*width == count";
+          return MPPI_ERR_INVALID_ARG;
+        }
+        mppi_status st = upload(costmap_d, data, count, stream, err);
+        auto& tex = cost.tex_helper_.textures_[0];
+        tex.data = costmap_d;
+        tex.height = dims[0];
+        tex.width = dims[1];
+        tex.use = (st == MPPI_OK);
+        return st;
+      }
+      /* updateOrigin / updateRotation / updateResolution: origin[3], rotations[9] row-major, resolution[3] */
+      if (name == "costmap_transform")
+      {
+        if (count != 15)
+        {
+          err = "costmap_transform: expected 15 floats (origin[3], rotations[9], resolution[3])";
+          return MPPI_ERR_INVALID_ARG;
+        }
+        auto& tex = cost.tex_helper_.textures_[0];
+        for (int i = 0; i < 3; i++)
+          tex.origin[i] = data[i];
+        for (int i = 0; i < 9; i++)
+          tex.rotations[i] = data[3 + i];
+        for (int i = 0; i < 3; i++)
+          tex.resolution[i] = data[12 + i];
+        return MPPI_OK;
       }
     }
     return ModelBase::setBlob(name, data, count, dims, ndims, stream, err);

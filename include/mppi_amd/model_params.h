@@ -15,6 +15,8 @@
  *   mppi_quadrotor_dynamics_params  <- QuadrotorDynamicsParams       dynamics/quadrotor/quadrotor_dynamics.cuh:10-63
  *   mppi_quadrotor_cost_params      <- QuadrotorQuadraticCostParams  cost_functions/quadrotor/quadrotor_quadratic_cost.cuh:10-70
  *                                      (CostParams<4> base; use_euler, the reference's bool, as an int)
+ *   mppi_quadrotor_map_cost_params  <- QuadrotorMapCostParams        cost_functions/quadrotor/quadrotor_map_cost.cuh:14-60
+ *                                      (CostParams<4> base; float3 / float4 as 3 / 4 floats each)
  * (paths relative to the reference's include/mppi/).
  */
 #ifndef MPPI_AMD_MODEL_PARAMS_H_
@@ -178,6 +180,41 @@ typedef struct mppi_quadrotor_cost_params
   float w_coeff;               /* 1 */
   float terminal_cost_coeff;   /* 0 */
 } mppi_quadrotor_cost_params;
+
+/** QuadrotorMapCost: the gate-racing cost over a track map.  The map itself and its frame are the "costmap" and
+ *  "costmap_transform" blobs of mppi_set_model_blob(); r_c1 / r_c2 / trs belong to the reference's legacy texture path, which its
+ *  device cost never reads, and are kept for the layout only.  Waypoints are x, y, z, heading; move them with the
+ *  updateWaypoint / updateGateBoundaries rule of the plugin's parameter class (or the Python mirror's), then set the block again. */
+typedef struct mppi_quadrotor_map_cost_params
+{
+  float control_cost_coeff[4]; /* {1, 1, 1, 1} */
+  float discount;              /* 1.0 */
+  float r_c1[3];               /* unused */
+  float r_c2[3];               /* unused */
+  float trs[3];                /* unused */
+  float attitude_coeff;        /* 10 */
+  float crash_coeff;           /* 1000 */
+  float dist_to_waypoint_coeff; /* 0 (not added by the device cost) */
+  float heading_coeff;         /* 5 */
+  float heading_power;         /* 1 */
+  float height_coeff;          /* 5 */
+  float track_coeff;           /* 10 */
+  float speed_coeff;           /* 5 */
+  float track_slop;            /* 0 */
+  float gate_pass_cost;        /* -150 */
+  float curr_waypoint[4];      /* 0 */
+  float prev_waypoint[4];      /* 0 */
+  float curr_gate_left[3];     /* 0 */
+  float curr_gate_right[3];    /* 0 */
+  float prev_gate_left[3];     /* 0 */
+  float prev_gate_right[3];    /* 0 */
+  float end_waypoint[4];       /* NaN */
+  float desired_speed;         /* 5 m/s */
+  float gate_margin;           /* 0.5 m */
+  float min_dist_to_gate_side; /* 0.5 m */
+  float track_boundary_cost;   /* 2.5 */
+  float gate_width;            /* 2.15 m */
+} mppi_quadrotor_map_cost_params;
 
 #ifdef __cplusplus
 }

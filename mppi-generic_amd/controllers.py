@@ -112,6 +112,96 @@ class QuadrotorQuadraticCostParams(C.Structure):
         self.terminal_cost_coeff = 0.0
 
 
+def _libm_f32(name):
+    """cosf / sinf of the C library, which the reference's host code and the C++ updateWaypoint call.  Looked up at the first
+    call; without a C math library it raises — another float32 cosine may differ in the last bit, and the gate posts would then
+    quietly stop matching the C++ class's"""
+    fn = []
+
+    def call(a):
+        if not fn:
+            import ctypes.util
+            try:
+                f = getattr(C.CDLL(ctypes.util.find_library("m") or "libm.so.6"), name)
+            except (OSError, AttributeError) as e:
+                raise OSError("QuadrotorMapCostParams.update_waypoint needs %s of the C math library: %s" % (name, e)) from e
+            f.restype, f.argtypes = C.c_float, [C.c_float]
+            fn.append(f)
+        return np.float32(fn[0](float(a)))
+    return call
+
+
+_cosf, _sinf = _libm_f32("cosf"), _libm_f32("sinf")
+
+
+class QuadrotorMapCostParams(C.Structure):
+    """mppi_quadrotor_map_cost_params (reference: cost_functions/quadrotor/quadrotor_map_cost.cuh:14-91); waypoints are
+    x, y, z, heading.  r_c1 / r_c2 / trs belong to the reference's legacy texture path and are unused; the track map and its frame
+    are the "costmap" / "costmap_transform" blobs (set_cost_texture)."""
+    _fields_ = [
+        ("control_cost_coeff", C.c_float * 4), ("discount", C.c_float),
+        ("r_c1", C.c_float * 3), ("r_c2", C.c_float * 3), ("trs", C.c_float * 3),
+        ("attitude_coeff", C.c_float), ("crash_coeff", C.c_float), ("dist_to_waypoint_coeff", C.c_float),
+        ("heading_coeff", C.c_float), ("heading_power", C.c_float), ("height_coeff", C.c_float), ("track_coeff", C.c_float),
+        ("speed_coeff", C.c_float), ("track_slop", C.c_float), ("gate_pass_cost", C.c_float),
+        ("curr_waypoint", C.c_float * 4), ("prev_waypoint", C.c_float * 4), ("curr_gate_left", C.c_float * 3),
+        ("curr_gate_right", C.c_float * 3), ("prev_gate_left", C.c_float * 3), ("prev_gate_right", C.c_float * 3),
+        ("end_waypoint", C.c_float * 4),
+        ("desired_speed", C.c_float), ("gate_margin", C.c_float), ("min_dist_to_gate_side", C.c_float),
+        ("track_boundary_cost", C.c_float), ("gate_width", C.c_float),
+    ]
+
+    def __init__(self):
+        super().__init__()
+        self.control_cost_coeff[:] = [1.0] * 4
+        self.discount = 1.0
+        self.r_c1[:], self.r_c2[:], self.trs[:] = [1, 0, 0], [0, 1, 0], [0, 0, 1]
+        self.attitude_coeff, self.crash_coeff, self.dist_to_waypoint_coeff = 10, 1000, 0.0
+        self.heading_coeff, self.heading_power, self.height_coeff = 5, 1.0, 5
+        self.track_coeff, self.speed_coeff, self.track_slop, self.gate_pass_cost = 10, 5, 0.0, -150
+        self.end_waypoint[:] = [float("nan")] * 4
+        self.desired_speed, self.gate_margin, self.min_dist_to_gate_side = 5, 0.5, 0.5
+        self.track_boundary_cost, self.gate_width = 2.5, 2.15
+
+    def update_waypoint(self, x, y, z, heading=0.0):
+        """QuadrotorMapCostParams::updateWaypoint (quadrotor_map_cost.cuh:62-75): a new waypoint moves current to previous and
+        places the gate's posts gate_width to either side along the heading, in float32 with the C library's cosf / sinf;
+        the same waypoint again changes nothing.  Returns whether it changed — push the block with setCostParams then."""
+        new = [np.float32(v) for v in (x, y, z, heading)]
+        if not any(np.float32(a) != b for a, b in zip(self.curr_waypoint, new)):
+            return False
+        self.prev_waypoint[:] = list(self.curr_waypoint)
+        self.curr_waypoint[:] = new
+        x, y, z, heading = new
+        gw, c, s = np.float32(self.gate_width), _cosf(heading), _sinf(heading)
+        self.update_gate_boundaries(x + c * gw, y + s * gw, z, x - c * gw, y - s * gw, z)
+        return True
+
+    def update_gate_boundaries(self, left_x, left_y, left_z, right_x, right_y, right_z):
+        """QuadrotorMapCostParams::updateGateBoundaries (quadrotor_map_cost.cuh:77-90)"""
+        left = [np.float32(v) for v in (left_x, left_y, left_z)]
+        right = [np.float32(v) for v in (right_x, right_y, right_z)]
+        if not any(np.float32(a) != b for a, b in zip(list(self.curr_gate_left) + list(self.curr_gate_right), left + right)):
+            return False
+        self.prev_gate_left[:] = list(self.curr_gate_left)
+        self.prev_gate_right[:] = list(self.curr_gate_right)
+        self.curr_gate_left[:] = left
+        self.curr_gate_right[:] = right
+        return True
+
+
+def set_cost_texture(controller, costmap, origin=(0.0, 0.0, 0.0), rotations=None, resolution=(1.0, 1.0, 1.0)):
+    """the map of a cost that samples it through a TwoDTextureHelper (QuadrotorMapCost): costmap [height][width], and its frame
+    — world origin of the map, world -> map rotation (3 x 3, row-major; identity when None), metres per texel — as the
+    "costmap" and "costmap_transform" blobs of mppi_set_model_blob"""
+    cm = _f32(costmap)
+    assert cm.ndim == 2, cm.shape
+    rot = np.eye(3, dtype=np.float32) if rotations is None else _f32(rotations).reshape(3, 3)
+    frame = np.concatenate([_f32(origin).reshape(3), rot.reshape(9), _f32(resolution).reshape(3)])
+    controller.setModelBlob("costmap_transform", frame)
+    controller.setModelBlob("costmap", cm)
+
+
 class RacerDubinsParams(C.Structure):
     """mppi_racer_dubins_params (reference: dynamics/racer_dubins/racer_dubins.cuh:67-87)"""
     _fields_ = [("c_t", C.c_float * 3), ("c_b", C.c_float * 3), ("c_v", C.c_float * 3), ("c_0", C.c_float),

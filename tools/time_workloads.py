@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Times optimisation iterations of the registered workloads for several block shapes (HIP events on the engine's
-stream).  Usage: python tools/time_workloads.py [cartpole|autorally|di|lstm|racer|quadrotor|nln|nln-gaussian] ...
+stream).  Usage: python tools/time_workloads.py [cartpole|autorally|di|lstm|racer|quadrotor|quadrotor-map|nln|nln-gaussian] ...
 (nln / nln-gaussian: the Cartpole pipeline kernel at K = 16384, T = 100 with the NLN and with the Gaussian sampler, one workload
 each so that a kernel trace of either holds one rollout kernel; not part of the default set.
 quadrotor: the reference's hover configuration at 2048 x 150 and 16384 x 150, each beside the double integrator at the same K and T
 — an analytic model on the same kernels, as the yardstick; not part of the default set either: the model's registration unit is
-examples/quadrotor_model/quadrotor_model.hip, built and loaded here)"""
+examples/quadrotor_model/quadrotor_model.hip, built and loaded here.
+quadrotor-map: QuadrotorMapCost on the three-gate course and track map of examples/templated_quadrotor_map.hip at the same two
+sizes, registration unit examples/quadrotor_model/quadrotor_map_model.hip; an argument ending in .so is another build of that
+unit to load in its place, for an A/B of two builds of the cost)"""
 import os
 import sys
 
@@ -83,3 +86,20 @@ if "quadrotor" in which:
         cfg["K"] = K
         run("quadrotor", cfg, [(64, 1, 1), (64, 1, 2), (32, 4, 1)], n=50)
         run("di", di_cfg(K=K, T=150, tube=False), [(64, 1, 1), (64, 1, 2)], n=50)
+if "quadrotor-map" in which:
+    import mppi_generic_amd as m  # noqa: E402
+    import quadrotor_map_oracle  # noqa: E402
+    from test_templated_quadrotor_map import course_map, course_params  # noqa: E402
+    other = [a for a in which if a.endswith(".so")]
+    if other:
+        assert m.load_library().mppi_load_plugin(os.path.abspath(other[0]).encode()) == m.MPPI_OK
+    else:
+        quadrotor_map_oracle.load_model(m)
+    values, frame = course_map()
+    x0 = np.zeros(13, np.float32)
+    x0[2], x0[6] = 1.0, 1.0
+    for K in (2048, 16384):
+        cfg = dict(model="quadrotor_map", K=K, T=150, D=1, dt=0.02, lambda_=5.0, alpha=0.0, num_iters=1, dyn=m.QuadrotorDynamicsParams(),
+                   cost=course_params(), ranges=None, std_dev=[0.5, 0.5, 0.5, 2.0], control_cost_coeff=[1.0] * 4, x0=x0,
+                   blobs={"costmap_transform": frame, "costmap": values})
+        run("quadrotor-map", cfg, [(64, 1, 1), (64, 1, 2), (32, 4, 1)], n=50)
