@@ -200,6 +200,13 @@ mppi_status mppi_register_model_checked(const char* name, int sampler_kind, mppi
                                         unsigned flags);
 /** dlopen()s a library whose static initialisers call mppi_register_model; the library stays loaded */
 mppi_status mppi_load_plugin(const char* path);
+/** takes a model's instantiation for one sampler kind out of the registry again: mppi_list_models / mppi_describe_model /
+ *  mppi_create no longer know it.  Handles created before keep working (a handle owns its model object); the plugin library
+ *  stays loaded.  Its static initialisers do not run a second time, so mppi_load_plugin of the same library puts back what
+ *  was unregistered of it.  MPPI_ERR_UNKNOWN_MODEL when
+ *  nothing is registered under (name, sampler_kind).  For processes that load a model for a while — a test module — and must
+ *  leave the registry as they found it. */
+mppi_status mppi_unregister_model(const char* name, int sampler_kind);
 /**
  * What a registered instantiation offers, without a handle and without a device: its block shapes and which kernel forms
  * exist for it (the table mppi_create chooses from).  shapes[capacity][4] receives (bx, by, bz, replicated) per registered
@@ -327,7 +334,9 @@ mppi_status mppi_set_nominal_threshold(mppi_handle h, float threshold);
  *   "dynamics_weights"  FNN parameters in the reference's blob order [W1 (out x in row-major) | b1 | W2 | b2 | ...]
  *                       (fnn_helper.cu:176-183); dims = {count}
  *   "costmap"           channel 0 of the track costmap, row-major [height][width]; dims = {height, width}.  The
- *                       world -> texture transform goes in the cost parameter block (r_c1, r_c2, trs).
+ *                       world -> texture transform goes in the cost parameter block (r_c1, r_c2, trs).  A cost that reads four
+ *                       channels (ARRobustCost) takes interleaved texels instead, [height][width][4]; dims =
+ *                       {height, width, 4}, and {height, width} is refused.
  */
 mppi_status mppi_set_model_blob(mppi_handle h, const char* name, const float* data, size_t count, const int* dims,
                                 int ndims);
@@ -358,7 +367,10 @@ mppi_status mppi_lstm_lstm_initialize(int init_input_dim, int init_hidden_dim, c
  *                    (the reference reads them from one archive with the prefixes "terra/mean_network/" and
  *                    "terra/uncertainty_network/", dynamics/racer_dubins/racer_dubins_elevation_lstm_unc.cu:30-33)
  *   kind "costmap"   ARStandardCost::loadTrackData (cost_functions/autorally/ar_standard_cost.cu:84-142): xBounds, yBounds,
- *                    pixelsPerMeter, channel0; also sets the world -> texture transform of the cost
+ *                    pixelsPerMeter, channel0; also sets the world -> texture transform of the cost.  A model whose cost reads
+ *                    all four channels of the track texture (ARRobustCost, "autorally_nn_robust") needs channel0 .. channel3
+ *                    of width * height values each: they are interleaved into {height, width, 4} texels (.x boundary
+ *                    constraint, .y track position, .z speed map, .w heading).  Other costs read channel0 alone
  * prefix may be NULL.  A git-LFS pointer file in place of the archive is reported as such.
  */
 mppi_status mppi_load_npz(mppi_handle h, const char* kind, const char* path, const char* prefix);

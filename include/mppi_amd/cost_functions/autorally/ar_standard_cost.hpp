@@ -54,15 +54,16 @@ public:
   int width_ = -1, height_ = -1;
 
   /** reference: ar_standard_cost.cu:211-222 */
-  __device__ inline void coorTransform(float x, float y, float* u, float* v, float* w) const
+  __host__ __device__ inline void coorTransform(float x, float y, float* u, float* v, float* w) const
   {
     u[0] = this->params_.r_c1[0] * x + this->params_.r_c2[0] * y + this->params_.trs[0];
     v[0] = this->params_.r_c1[1] * x + this->params_.r_c2[1] * y + this->params_.trs[1];
     w[0] = this->params_.r_c1[2] * x + this->params_.r_c2[2] * y + this->params_.trs[2];
   }
 
-  /** point-sampled, clamped, normalised-coordinate fetch of channel 0 (ar_standard_cost.cu:224-243 device branch) */
-  __device__ inline float queryTextureTransformed(float x, float y) const
+  /** the texel a world position falls into, as iy * width_ + ix: point sampling with clamp addressing on normalised coordinates
+   *  (ar_standard_cost.cu:224-243 device branch).  The one statement of the rule: ARRobustCost's four-channel fetch uses it too */
+  __host__ __device__ inline int texelIndexTransformed(float x, float y) const
   {
     float u, v, w;
     coorTransform(x, y, &u, &v, &w);
@@ -70,7 +71,13 @@ public:
     const float fy = floorf(v / w * (float)height_);
     int ix = (fx >= 0.0f) ? ((fx < (float)width_) ? (int)fx : width_ - 1) : 0;   // NaN -> 0
     int iy = (fy >= 0.0f) ? ((fy < (float)height_) ? (int)fy : height_ - 1) : 0;
-    return costmap_d_[iy * width_ + ix];
+    return iy * width_ + ix;
+  }
+
+  /** point-sampled, clamped, normalised-coordinate fetch of channel 0 */
+  __device__ inline float queryTextureTransformed(float x, float y) const
+  {
+    return costmap_d_[texelIndexTransformed(x, y)];
   }
 
   __device__ inline float terminalCost(float* s, float* theta_c)

@@ -264,6 +264,11 @@ struct ModelBase
   {
     return false;
   }
+  /** channels of the "costmap" blob of a cost with costmap_d_: 1 {height, width}, 4 {height, width, 4}; 0: the cost has none */
+  virtual int costmapChannels() const
+  {
+    return 0;
+  }
 };
 
 /** fingerprint of the structures a model translation unit and libmppi_amd.so exchange (mppi_register_model refuses a
@@ -273,8 +278,8 @@ struct ModelBase
  *  3: rows-in-HBM arguments; 4: release-flag arguments of the finalize kernels (both round 3); 5: supportsStreamedMerge (round 4);
  *  6: FinalizeArgs::phases / carry block of the split hand-over (round 5); 7: undeclaredBarrierFreePlugins; 8: the transposed
  *  record copy (RolloutArgs) and supportsMergeControl / launchMergeControl (both round 6); 9: LaunchRecord,
- *  listReplicatedLaneShapes / supportsRMPPIPipeline (the launch and model introspection of mppi_amd.h). */
-#define MPPI_ENGINE_ABI_VERSION 9
+ *  listReplicatedLaneShapes / supportsRMPPIPipeline (the launch and model introspection of mppi_amd.h); 10: costmapChannels. */
+#define MPPI_ENGINE_ABI_VERSION 10
 
 constexpr int engineAbiFingerprint()
 {
@@ -443,6 +448,16 @@ struct has_costmap : std::false_type
 };
 template <class T>
 struct has_costmap<T, std::void_t<decltype(std::declval<T&>().costmap_d_)>> : std::true_type
+{
+};
+/** channels of a has_costmap cost's map: `static constexpr int COSTMAP_CHANNELS = 4;` in the class (ARRobustCost: interleaved
+ *  float[height][width][4] texels); absent: 1, a plain float[height][width] (ARStandardCost) */
+template <class T, class = void>
+struct costmap_channels : std::integral_constant<int, 1>
+{
+};
+template <class T>
+struct costmap_channels<T, std::void_t<decltype(T::COSTMAP_CHANNELS)>> : std::integral_constant<int, T::COSTMAP_CHANNELS>
 {
 };
 template <class T, class = void>
@@ -1184,10 +1199,24 @@ struct ModelT : ModelBase
     {
       if (name == "costmap")
       {
-        if (ndims != 2 || dims[0] <= 0 || dims[1] <= 0 || (size_t)dims[0] * dims[1] != count)
+        constexpr int CH = costmap_channels<COST_T>::value;
+        if constexpr (CH == 1)
         {
-          err = "costmap: dims must be {height, width} with height*width == count";
-          return MPPI_ERR_INVALID_ARG;
+          if (ndims != 2 || dims[0] <= 0 || dims[1] <= 0 || (size_t)dims[0] * dims[1] != count)
+          {
+            err = "costmap: dims must be {height, width} with height*width == count";
+            return MPPI_ERR_INVALID_ARG;
+          }
+        }
+        else
+        {
+          /* interleaved texels, one CH-float texel per map cell (ARRobustCost: boundary, track position, speed, heading) */
+          if (ndims != 3 || dims[0] <= 0 || dims[1] <= 0 || dims[2] != CH || (size_t)dims[0] * dims[1] * CH != count)
+          {
+            err = "costmap: this model's cost reads " + std::to_string(CH) + " channels: dims must be {height, width, " +
+                  std::to_string(CH) + "} (interleaved texels) with height*width*" + std::to_string(CH) + " == count";
+            return MPPI_ERR_INVALID_ARG;
+          }
         }
         mppi_status st = upload(costmap_d, data, count, stream, err);
         cost.costmap_d_ = costmap_d;
@@ -1267,6 +1296,12 @@ struct ModelT : ModelBase
     return ModelBase::setLSTMInitialState(hidden, cell, stream, err);
   }
 
+  int costmapChannels() const override
+  {
+    if constexpr (has_costmap<COST_T>::value)
+      return costmap_channels<COST_T>::value;
+    return 0;
+  }
   mppi_status setCostmapTransform(const float* r_c1, const float* r_c2, const float* trs) override
   {
     if constexpr (has_costmap<COST_T>::value)

@@ -17,6 +17,8 @@
  *                                      (CostParams<4> base; use_euler, the reference's bool, as an int)
  *   mppi_quadrotor_map_cost_params  <- QuadrotorMapCostParams        cost_functions/quadrotor/quadrotor_map_cost.cuh:14-60
  *                                      (CostParams<4> base; float3 / float4 as 3 / 4 floats each)
+ *   mppi_ar_robust_cost_params      <- ARRobustCostParams            cost_functions/autorally/ar_robust_cost.cuh:6-29
+ *                                      (ARStandardCostParams base + heading_coeff)
  * (paths relative to the reference's include/mppi/).
  */
 #ifndef MPPI_AMD_MODEL_PARAMS_H_
@@ -156,6 +158,27 @@ typedef struct mppi_ar_standard_cost_params
   float r_c2[3];               /* column 2 */
   float trs[3];                /* translation */
 } mppi_ar_standard_cost_params;
+
+/** <- ARRobustCostParams  cost_functions/autorally/ar_robust_cost.cuh:6-29: the standard block with other defaults and a trailing
+ *  heading_coeff.  The costmap of this cost is the four-channel "costmap" blob, dims {height, width, 4}. */
+typedef struct mppi_ar_robust_cost_params
+{
+  float control_cost_coeff[2]; /* {0, 0} */
+  float discount;              /* 1.0 */
+  float desired_speed;         /* -1: the map's speed channel is the target */
+  float speed_coeff;           /* 20 */
+  float track_coeff;           /* 33 */
+  float max_slip_ang;          /* 1.5 */
+  float slip_coeff;            /* 0 */
+  float track_slop;            /* 0 */
+  float crash_coeff;           /* 125000 */
+  float boundary_threshold;    /* 0.75 */
+  int grid_res;                /* 10 */
+  float r_c1[3];               /* world -> texture transform, column 1 */
+  float r_c2[3];               /* column 2 */
+  float trs[3];                /* translation */
+  float heading_coeff;         /* 0 */
+} mppi_ar_robust_cost_params;
 
 typedef struct mppi_quadrotor_dynamics_params
 {

@@ -91,6 +91,7 @@ SIGNATURES = {
     "mppi_register_model": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_int]),
     "mppi_register_model_checked": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_int, C.c_uint]),
     "mppi_load_plugin": (C.c_int, [C.c_char_p]),
+    "mppi_unregister_model": (C.c_int, [C.c_char_p, C.c_int]),
     "mppi_describe_model": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
                                       C.POINTER(C.c_uint)]),
     "mppi_create": (C.c_int, [C.POINTER(MppiConfig), C.POINTER(H)]),

@@ -339,6 +339,33 @@ class ARStandardCostParams(C.Structure):
         self.trs[:] = [-x_min / (x_max - x_min), -y_min / (y_max - y_min), 1]
 
 
+class ARRobustCostParams(C.Structure):
+    """mppi_ar_robust_cost_params (reference: cost_functions/autorally/ar_robust_cost.cuh:6-29): ARStandardCostParams' fields with
+    the robust cost's defaults, then heading_coeff.  The model's "costmap" blob is [height][width][4] interleaved texels
+    (boundary constraint, track position, speed map, heading)."""
+    _fields_ = ARStandardCostParams._fields_ + [("heading_coeff", C.c_float)]
+
+    def __init__(self):
+        super().__init__()
+        self.control_cost_coeff[:] = [0.0, 0.0]
+        self.discount = 1.0
+        self.desired_speed = -1
+        self.speed_coeff = 20.0
+        self.track_coeff = 33.0
+        self.max_slip_ang = 1.5
+        self.slip_coeff = 0.0
+        self.track_slop = 0
+        self.crash_coeff = 125000
+        self.boundary_threshold = 0.75
+        self.grid_res = 10
+        self.r_c1[:] = [1, 0, 0]
+        self.r_c2[:] = [0, 1, 0]
+        self.trs[:] = [0, 0, 1]
+        self.heading_coeff = 0.0
+
+    setTransformFromBounds = ARStandardCostParams.setTransformFromBounds
+
+
 def fnn_blob_from_npz_dict(d, prefix="dynamics_"):
     """flat FNN parameter blob [W1|b1|W2|b2|...] from the reference's .npz key layout (dynamics_W{i}, dynamics_b{i},
     float64; FNNHelper::loadParams, utils/nn_helpers/fnn_helper.cu:96-174)"""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times optimisation iterations of the registered workloads for several block shapes (HIP events on the engine's
-stream).  Usage: python tools/time_workloads.py [cartpole|autorally|di|lstm|racer|quadrotor|quadrotor-map|nln|nln-gaussian] ...
+stream).  Usage: python tools/time_workloads.py [cartpole|autorally|autorally-robust|di|lstm|racer|quadrotor|quadrotor-map|nln|nln-gaussian] ...
 (nln / nln-gaussian: the Cartpole pipeline kernel at K = 16384, T = 100 with the NLN and with the Gaussian sampler, one workload
 each so that a kernel trace of either holds one rollout kernel; not part of the default set.
 quadrotor: the reference's hover configuration at 2048 x 150 and 16384 x 150, each beside the double integrator at the same K and T
@@ -8,7 +8,12 @@ quadrotor: the reference's hover configuration at 2048 x 150 and 16384 x 150, ea
 examples/quadrotor_model/quadrotor_model.hip, built and loaded here.
 quadrotor-map: QuadrotorMapCost on the three-gate course and track map of examples/templated_quadrotor_map.hip at the same two
 sizes, registration unit examples/quadrotor_model/quadrotor_map_model.hip; an argument ending in .so is another build of that
-unit to load in its place, for an A/B of two builds of the cost)"""
+unit to load in its place, for an A/B of two builds of the cost.
+autorally-robust: "autorally_nn_robust" (ARRobustCost on a four-channel 600 x 600 map over the standard track map's extent) at
+K = 16384, T = 150 — the vanilla iteration on the default MFMA shape, fused and role-pipelined, and Robust MPPI's computeControl
+(wall clock around the call, which returns after the control is on the host) — each beside "autorally_nn" with ARStandardCost in
+the same run, as the yardstick; registration unit examples/autorally_robust_model/autorally_robust_model.hip, or an argument ending
+in .so)"""
 import os
 import sys
 
@@ -103,3 +108,42 @@ if "quadrotor-map" in which:
                    cost=course_params(), ranges=None, std_dev=[0.5, 0.5, 0.5, 2.0], control_cost_coeff=[1.0] * 4, x0=x0,
                    blobs={"costmap_transform": frame, "costmap": values})
         run("quadrotor-map", cfg, [(64, 1, 1), (64, 1, 2), (32, 4, 1)], n=50)
+if "autorally-robust" in which:
+    import time  # noqa: E402
+    import mppi_generic_amd as m  # noqa: E402
+    import ar_robust_oracle  # noqa: E402
+    from common import SEED, standard_track_map  # noqa: E402
+    other = [a for a in which if a.endswith(".so")]
+    if other:
+        assert m.load_library().mppi_load_plugin(os.path.abspath(other[0]).encode()) == m.MPPI_OK
+    else:
+        ar_robust_oracle.load_model(m)
+    std = autorally_cfg(K=16384, T=150, lambda_=1.0)
+    track, bounds = standard_track_map()
+    # boundary constraint rising to 1 away from the centre line, the standard map as the track position, 4 m/s, heading 0
+    texels = ar_robust_oracle.interleave([np.clip(track / 10.0, 0.0, 1.0), track, np.full_like(track, 4.0), np.zeros_like(track)])
+    cost = m.ARRobustCostParams()
+    cost.setTransformFromBounds(*bounds)
+    cost.heading_coeff = 5.0
+    rob = dict(std, model="autorally_nn_robust", cost=cost, blobs={"dynamics_weights": std["blobs"]["dynamics_weights"], "costmap": texels})
+    for name, cfg in (("ar-robust", rob), ("autorally", std)):
+        run(name, cfg, [(0, 0, 1), (0, 0, 2)], n=30)
+    gains = np.random.default_rng(5).uniform(-0.3, 0.3, (150, 7, 2)).astype(np.float32)
+    for name, cfg in (("ar-robust", rob), ("autorally", std)):
+        eng = m.RobustMPPIController(cfg["model"], cfg["K"], cfg["T"], cfg["dt"], cfg["lambda_"], cfg["alpha"], 1, seed=SEED)
+        eng.setCostParams(cfg["cost"])
+        for blob, arr in cfg["blobs"].items():
+            eng.setModelBlob(blob, arr)
+        eng.setControlRanges(cfg["ranges"])
+        eng.setSamplingParams(cfg["std_dev"], [0.2, 0.1], 0.01, 1.0)
+        eng.setRMPPIParams(1000.0, 9, 32)
+        eng.updateImportanceSamplingControl(cfg["x0"], 1)
+        eng.setFeedbackGains(gains)
+        for _ in range(5):
+            eng.computeControl(cfg["x0"], 1)
+        t0 = time.perf_counter()
+        for _ in range(30):
+            eng.computeControl(cfg["x0"], 1)
+        us = (time.perf_counter() - t0) / 30 * 1e6
+        print("%-10s K=%d T=%d Robust computeControl %.1f us (%s)" % (name, cfg["K"], cfg["T"], us, eng.getLaunchInfo()["family"]), flush=True)
+        eng.close()
