@@ -590,7 +590,9 @@ mppi_status mppi_measure_launch_boundary(int device, int n, float* us_per_launch
  */
 mppi_status mppi_measure_issue_interval(int device, float* ns_per_instruction);
 /** elementwise det_math on the device (func ids 0-13 as oracle_det_eval): host/device bit-parity test hook.
- *  func 14 exists on the engine side only: it is det::atan2 and takes its two arguments as (y, x) pairs: y[2j] = y[2j + 1] = atan2(x[2j], x[2j + 1]) */
+ *  func 14 exists on the engine side only: it is det::atan2 and takes its two arguments as (y, x) pairs: y[2j] = y[2j + 1] = atan2(x[2j], x[2j + 1]);
+ *  func 15, engine side only as well: the merge's quotient helpers (engine/merge_wave.hpp) on (p, q) pairs, n even:
+ *  y[2k] = mergeQuotient(p_k, q_k), y[2k + 1] = entry k & 3 of mergeQuotients((p_k .. p_k+3, pairs wrapping), q_k) */
 mppi_status mppi_det_eval(int func, const float* x, float* y, int n, int device);
 
 /** geometry / sampling state of one 2-D map (reference: TextureParams, utils/texture_helpers/texture_helper.cuh:17-63) */

@@ -312,7 +312,13 @@ __global__ void __launch_bounds__(pipelineBlockX(BZ, FOLD_Z) * (FOLD_Z ? 1 : BZ)
   typedef float merge_f2 __attribute__((ext_vector_type(2)));
   merge_f2 tailq[MERGE_LANE_RECORDS];
   const int TC_all = num_timesteps * C;
-  auto load_trip_columns = [&](const int t) {
+  // FULL (round 9): every lane's MERGE_LANE_RECORDS record slots are filled (args.prev_num_records == 64 * MERGE_LANE_RECORDS, the
+  // headline's 256 blocks) — no padding record, so no `ok` select on a tail or on a column value, and the quads' addresses are a
+  // wave-uniform base plus a lane offset that never changes.  The comparison is made once per launch (full_records below) and a
+  // trip takes one scalar branch on it, around the merge alone: the draw and the shaping exist once.  (Two copies of the whole
+  // sampler loop — the branch outside the trips — moved blocks of every role loop of the kernel and cost the dynamics wave's
+  // 8-step loop its layout.)  Every other record count takes the select path.
+  auto load_trip_columns = [&](const int t, auto full) {
     if constexpr (STREAM_MERGE)
     {
       // the transposed copy of the records (RolloutArgs::records_t_d): quad q of record b at [q][b][4] — a load instruction's 64
@@ -322,17 +328,29 @@ __global__ void __launch_bounds__(pipelineBlockX(BZ, FOLD_Z) * (FOLD_Z ? 1 : BZ)
       for (int g = 0; g < TRIP_GROUPS; g++)
       {
         const int col0 = t * C + MERGE_COLS * g;  // T*C is a multiple of 4 (engine): a quad lies inside the record or behind it
-#pragma unroll
-        for (int i = 0; i < MERGE_LANE_RECORDS; i++)
+        if constexpr (decltype(full)::value)
         {
-          const int b = lane + 64 * i;
-          const bool ok = b < args.prev_num_records && col0 < TC_all;  // (else: any valid address; the value is not used)
-          vq[g][i] = *reinterpret_cast<const merge_f4*>(args.prev_records_t_d +
-                                                        ((size_t)(ok ? col0 >> 2 : 0) * args.prev_num_records + (ok ? b : 0)) * 4);
+          constexpr int RECORDS = 64 * MERGE_LANE_RECORDS;
+          const float* quad = args.prev_records_t_d + (size_t)(col0 < TC_all ? col0 >> 2 : 0) * (RECORDS * 4) + 4 * lane;
+#pragma unroll
+          for (int i = 0; i < MERGE_LANE_RECORDS; i++)
+            vq[g][i] = *reinterpret_cast<const merge_f4*>(quad + 4 * 64 * i);
+        }
+        else
+        {
+#pragma unroll
+          for (int i = 0; i < MERGE_LANE_RECORDS; i++)
+          {
+            const int b = lane + 64 * i;
+            const bool ok = b < args.prev_num_records && col0 < TC_all;  // (else: any valid address; the value is not used)
+            vq[g][i] = *reinterpret_cast<const merge_f4*>(args.prev_records_t_d +
+                                                          ((size_t)(ok ? col0 >> 2 : 0) * args.prev_num_records + (ok ? b : 0)) * 4);
+          }
         }
       }
     }
   };
+  const bool full_records = STREAM_MERGE && args.prev_num_records == 64 * MERGE_LANE_RECORDS;
   auto sampler_trip = [&](const int t, auto first_trip) {
     constexpr int QUADS = C;  // SMP_STEPS * C / 4
     float zq[4 * QUADS];
@@ -371,30 +389,40 @@ __global__ void __launch_bounds__(pipelineBlockX(BZ, FOLD_Z) * (FOLD_Z ? 1 : BZ)
       }
       PIPE_T(if (decltype(first_trip)::value && smp_id == 0) tm.trip(block_idx, 4, 2, lane, __builtin_amdgcn_s_memtime() - tm.t0);)
       // this trip's part of u* of the previous iteration: the merge kernel's arithmetic on the quads loaded a trip ago
+      auto merge_trip = [&](auto full) {
+        constexpr bool FULL = decltype(full)::value;
 #pragma unroll
-      for (int g = 0; g < TRIP_GROUPS; g++)
-      {
-        float v[MERGE_LANE_RECORDS][MERGE_COLS], tot[MERGE_COLS];
-#pragma unroll
-        for (int i = 0; i < MERGE_LANE_RECORDS; i++)
+        for (int g = 0; g < TRIP_GROUPS; g++)
         {
-          const bool ok = lane + 64 * i < args.prev_num_records;  // a padding record counts as zeros (combineWave's rule)
-          v[i][0] = ok ? vq[g][i].x : 0.0f;
-          v[i][1] = ok ? vq[g][i].y : 0.0f;
-          v[i][2] = ok ? vq[g][i].z : 0.0f;
-          v[i][3] = ok ? vq[g][i].w : 0.0f;
-        }
-        mergeColumns(mt.s, v, tot);
+          float v[MERGE_LANE_RECORDS][MERGE_COLS], tot[MERGE_COLS], quot[MERGE_COLS];
 #pragma unroll
-        for (int c = 0; c < MERGE_COLS; c++)
-        {
-          mu[MERGE_COLS * g + c] = tot[c] / mt.eta_f;
-          if (t * C + MERGE_COLS * g + c < TC_all)
-            mean_row_s[t * C + MERGE_COLS * g + c] = mu[MERGE_COLS * g + c];  // every lane: same word, same value
+          for (int i = 0; i < MERGE_LANE_RECORDS; i++)
+          {
+            const bool ok = FULL || lane + 64 * i < args.prev_num_records;  // a padding record counts as zeros (combineWave's rule)
+            v[i][0] = ok ? vq[g][i].x : 0.0f;
+            v[i][1] = ok ? vq[g][i].y : 0.0f;
+            v[i][2] = ok ? vq[g][i].z : 0.0f;
+            v[i][3] = ok ? vq[g][i].w : 0.0f;
+          }
+          mergeColumns(mt.s, v, tot);
+          mergeQuotients(tot, mt.etaDivisor(), quot);  // tot[c] / mt.eta_f, the divisor's reciprocal prepared once (merge_wave.hpp)
+#pragma unroll
+          for (int c = 0; c < MERGE_COLS; c++)
+            mu[MERGE_COLS * g + c] = quot[c];
+          // one 16-byte store of the quad (every lane: same words, same values).  t * C and T * C are multiples of 4 (a trip starts
+          // at a multiple of SMP_STEPS; the engine streams only such T * C), so the quad lies inside [T][C] or behind it as a whole,
+          // and mean_row_s sits at a multiple of 16 bytes: every region in front of it is a whole number of 16-byte units.
+          static_assert(SMP_STEPS % 4 == 0 && MERGE_COLS == 4, "a trip's quads start at multiples of four columns");
+          if (t * C + MERGE_COLS * g < TC_all)
+            *reinterpret_cast<merge_f4*>(mean_row_s + t * C + MERGE_COLS * g) = merge_f4{ quot[0], quot[1], quot[2], quot[3] };
         }
-      }
-      PIPE_T(if (decltype(first_trip)::value && smp_id == 0) tm.trip(block_idx, 4, 3, lane, __builtin_amdgcn_s_memtime() - tm.t0);)
-      load_trip_columns(t + SMP_STEPS * NS);  // the quads of this wave's next trip: in flight until then
+        PIPE_T(if (decltype(first_trip)::value && smp_id == 0) tm.trip(block_idx, 4, 3, lane, __builtin_amdgcn_s_memtime() - tm.t0);)
+        load_trip_columns(t + SMP_STEPS * NS, full);  // the quads of this wave's next trip: in flight until then
+      };
+      if (full_records)
+        merge_trip(std::true_type{});
+      else
+        merge_trip(std::false_type{});
     }
 #pragma unroll
     for (int s2 = 0; s2 < SMP_STEPS; s2++)
@@ -429,7 +457,7 @@ __global__ void __launch_bounds__(pipelineBlockX(BZ, FOLD_Z) * (FOLD_Z ? 1 : BZ)
         const int b = lane + 64 * i;
         tailq[i] = *reinterpret_cast<const merge_f2*>(tails_t + 2 * (b < args.prev_num_records ? b : 0));
       }
-      load_trip_columns(SMP_STEPS * smp_id);
+      load_trip_columns(SMP_STEPS * smp_id, std::false_type{});  // (either form: the same addresses)
       asm volatile("" ::: "memory");  // the loads are issued here, not sunk to their first use behind the draw
       PIPE_T(if (smp_id == 0) tm.trip(block_idx, 4, 0, lane, __builtin_amdgcn_s_memtime() - tm.t0);)
     }

@@ -264,6 +264,24 @@ __global__ void detEvalKernel(int func, const float* x, float* y, int n)
         r = mppi::det::atan2(x[j], j + 1 < n ? x[j + 1] : 1.0f);
         break;
       }
+      case 15:  // the merge's quotient helpers (engine/merge_wave.hpp); x holds (p, q) pairs, n even.  Pair k: y[2k] = the single
+      {         // quotient p_k / q_k; y[2k + 1] = entry c = k & 3 of the packed quad (p_k, p_k+1, p_k+2, p_k+3) / q_k, pairs wrapping
+        const int pairs = n / 2, k = i / 2;
+        if (k >= pairs)
+          break;
+        const mppi::kernels::MergeDivisor d = mppi::kernels::mergeDivisor(x[2 * k + 1]);
+        if (!(i & 1))
+        {
+          r = mppi::kernels::mergeQuotient(x[2 * k], d);
+          break;
+        }
+        float p[mppi::kernels::MERGE_COLS], out[mppi::kernels::MERGE_COLS];
+        for (int c = 0; c < mppi::kernels::MERGE_COLS; c++)
+          p[c] = x[2 * ((k + c) % pairs)];
+        mppi::kernels::mergeQuotients(p, d, out);
+        r = out[k & 3];
+        break;
+      }
     }
     y[i] = r;
   }

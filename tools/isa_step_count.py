@@ -30,6 +30,11 @@ KERNELS = [
      ("ds_write2st64_b32", None)),  # round 4: eight steps per trip
     ("cartpole_pipeline_cost_wave", "cartpole.hip", CARTPOLE_HEADLINE, 4, "valu_pk",
      ("ds_read2st64_b32", "ds_write2st64_b32")),  # four steps per trip
+    # round 9: a sampler wave's steady-state trip (four steps): the loop that loads the next trip's column quads.  A STATIC count
+    # of everything between the loop's head and its backward branch: both arms of the merge (all record slots filled / padding
+    # selects) and the `/` fall-backs of merge_wave.hpp's quotients, of which a trip executes one arm and no fall-back
+    ("cartpole_pipeline_sampler_wave", "cartpole.hip", CARTPOLE_HEADLINE, 4, "xlane",
+     ("global_load_dwordx4", "ds_write2st64_b32")),
     ("autorally_mfma_pipeline_dynamics_wave", "autorally_nn.hip",
      ["rolloutPipelineRepKernel", "NeuralNetModelMFMA", "GaussianDistribution", "ELb1ELb0EE"], None, "mfma"),
     ("lstm_mfma_pipeline_dynamics_wave", "bicycle_slip_lstm.hip",
@@ -59,7 +64,12 @@ def loops_of(tu, keys):
                     simm -= 0x10000
                 tgt = ad + 4 + simm * 4
                 if tgt < ad and tgt in addr and addr[ad] - addr[tgt] + 1 >= 40:
-                    loops.append([o for _, o, _ in ins[addr[tgt]:addr[ad] + 1]])
+                    ops = [o for _, o, _ in ins[addr[tgt]:addr[ad] + 1]]
+                    # a span with a workgroup barrier in it is no wave's step loop: it is a cold block the compiler has laid
+                    # out behind the role loops (round 9: the `/` fall-back of the sampler waves' first trip, which runs in
+                    # front of the block's barriers) branching back to where it came from
+                    if "s_barrier" not in ops:
+                        loops.append(ops)
         out.append((lines[a][18:], loops))
     return out
 
