@@ -33,7 +33,7 @@ extern "C" {
 #endif
 
 #define MPPI_AMD_VERSION_MAJOR 0
-#define MPPI_AMD_VERSION_MINOR 2
+#define MPPI_AMD_VERSION_MINOR 3 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory */
 
 typedef struct mppi_handle_s* mppi_handle;
 
@@ -431,6 +431,27 @@ mppi_status mppi_get_costs(mppi_handle h, float* costs);
 mppi_status mppi_get_stats(mppi_handle h, mppi_stats* out);
 /** clamped samples v[D][K_local][T][C] of the last iteration (control_samples_d_); needs cfg.save_samples */
 mppi_status mppi_get_sampled_controls(mppi_handle h, float* v);
+
+/* ---------------------------------------------------------------- linearisation ---------------------------------- */
+/* The continuous-time Jacobians of the model, A = d xdot / d x [S][S] and B = d xdot / d u [S][C], both row-major
+ * (A[i][j] = d xdot_i / d x_j) — Dynamics::computeGrad(state, control, A, B) of the reference (dynamics/dynamics.cuh:239), what
+ * its DDP feedback is built from (ddp/ddp_model_wrapper.h:26); the caller forms I + A dt.  Evaluated on the device by the
+ * model's own computeGrad (mppi_amd/plugin/dynamics.hpp), all points in one launch on the handle's stream behind whatever is
+ * queued there (mppi_amd/engine/linearize_kernel.hpp).  Nothing the controller computes depends on these calls. */
+/** 1 when the model's Dynamics class declares a device computeGrad, else 0 (also for a null handle) */
+int mppi_has_compute_grad(mppi_handle h);
+/** A_out[n][S][S], B_out[n][S][C] at the n >= 1 points x[n][S], u[n][C], all host arrays.  MPPI_ERR_INVALID_ARG for n <= 0 or a
+ *  null pointer, MPPI_ERR_UNSUPPORTED for a model without computeGrad; message in mppi_last_error. */
+mppi_status mppi_linearize(mppi_handle h, const float* x, const float* u, int n, float* A_out, float* B_out);
+/**
+ * A_out[T][S][S], B_out[T][S][C] along the result of the last mppi_compute_control, read where the device left it (no host round
+ * trip for the inputs): pair t is (state t, control t) of
+ *   system 0   the sequences mppi_get_state_seq / mppi_get_control_seq return
+ *   system 1   Tube / Robust: the nominal ones (mppi_get_nominal_state_seq / mppi_get_nominal_control_seq)
+ * as of that call — mppi_slide shifts the host copies only.  MPPI_ERR_STATE before the first mppi_compute_control,
+ * MPPI_ERR_INVALID_ARG for system 1 on a one-system controller or any other system, MPPI_ERR_UNSUPPORTED as above.
+ */
+mppi_status mppi_linearize_trajectory(mppi_handle h, int system, float* A_out, float* B_out);
 
 /* ---------------------------------------------------------------- Robust MPPI (MPPI_CONTROLLER_ROBUST) ----------- */
 /* Systems of a Robust-MPPI handle: 0 = nominal, 1 = real (robust_mppi_controller.cu:637-640); x0 of

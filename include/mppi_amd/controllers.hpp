@@ -175,6 +175,27 @@ public:
     check(mppi_get_state_seq(h_, x.data()));
     return x;
   }
+  /** the model's Dynamics class declares a device computeGrad (mppi_has_compute_grad) */
+  bool hasComputeGrad() const
+  {
+    return mppi_has_compute_grad(h_) != 0;
+  }
+  /** Dynamics::computeGrad at n points on the device (mppi_linearize): states[n][S], controls[n][C] -> A[n][S][S], B[n][S][C],
+   *  row-major, continuous time */
+  void computeGrad(const float* states, const float* controls, int n, std::vector<float>& A, std::vector<float>& B) const
+  {
+    A.resize((size_t)(n > 0 ? n : 0) * state_dim_ * state_dim_);
+    B.resize((size_t)(n > 0 ? n : 0) * state_dim_ * control_dim_);
+    check(mppi_linearize(h_, states, controls, n, A.data(), B.data()));
+  }
+  /** A[T][S][S], B[T][S][C] along the result of the last computeControl (mppi_linearize_trajectory; system 1: the nominal
+   *  sequences of a Tube / Robust controller) */
+  void computeGradTrajectory(std::vector<float>& A, std::vector<float>& B, int system = 0) const
+  {
+    A.resize((size_t)num_timesteps_ * state_dim_ * state_dim_);
+    B.resize((size_t)num_timesteps_ * state_dim_ * control_dim_);
+    check(mppi_linearize_trajectory(h_, system, A.data(), B.data()));
+  }
   std::vector<float> getTargetOutputSeq() const
   {
     std::vector<float> y((size_t)num_timesteps_ * output_dim_);

@@ -240,6 +240,27 @@ public:
       check(mppi_get_control_seq(h_, u.data()));
     return u;
   }
+  /** the reference's model_->computeGrad(state, control, A, B) (dynamics/dynamics.cuh:239), evaluated on the device by DYN_T's
+   *  own method (mppi_linearize): A[S][S] = d xdot / d x and B[S][C] = d xdot / d u, row-major.  false, nothing written: DYN_T
+   *  declares no device computeGrad (plugin/dynamics.hpp). */
+  bool computeGrad(const state_array& state, const control_array& control, float* A, float* B)
+  {
+    if (!mppi::has_compute_grad<DYN_T>::value)
+      return false;
+    ensureHandle();
+    syncPlugins();
+    check(mppi_linearize(h_, state.data(), control.data(), 1, A, B));
+    return true;
+  }
+  /** the same at every step of the last computeControl's result, read on the device (mppi_linearize_trajectory):
+   *  A[t] = &A[t * S * S], B[t] = &B[t * S * C]; system 1: the nominal sequences of a Tube / Robust controller */
+  void computeGradTrajectory(std::vector<float>& A, std::vector<float>& B, int system = 0)
+  {
+    ensureHandle();
+    A.resize((size_t)params_.num_timesteps_ * STATE_DIM * STATE_DIM);
+    B.resize((size_t)params_.num_timesteps_ * STATE_DIM * CONTROL_DIM);
+    check(mppi_linearize_trajectory(h_, system, A.data(), B.data()));
+  }
   state_trajectory getTargetStateSeq() const
   {
     state_trajectory x = state_trajectory::Zero();

@@ -12,6 +12,7 @@
 #include "mppi_amd/utils/nn_helpers/fnn_helper.hpp"
 #include "mppi_amd/utils/nn_helpers/fnn_mfma.hpp"
 #include "mppi_amd/utils/nn_helpers/fnn_wave.hpp"
+#include "mppi_amd/utils/nn_helpers/fnn_grad_wave.hpp"
 
 struct NNDynamicsParams : public DynamicsParams
 {
@@ -48,8 +49,85 @@ struct NNDynamicsParams : public DynamicsParams
 
 using namespace MPPI_internal;
 
+/**
+ * Dynamics::computeGrad of the AutoRally model for every form of it below (reference: ar_nn_model.cu:64-88): the three kinematic
+ * rows, then the network's input Jacobian (utils/nn_helpers/fnn_grad_wave.hpp) under the dynamic states — its first DYNAMICS_DIM
+ * columns into A, the control columns into B.  One wave per point: all 64 lanes call with the same arguments and write the same
+ * values.  theta: the parameter blob the forms share, staged in LDS by initializeGrad().  A, B arrive zeroed.
+ */
 template <int S_DIM, int C_DIM, int K_DIM>
-class NeuralNetModel : public Dynamics<NeuralNetModel<S_DIM, C_DIM, K_DIM>, NNDynamicsParams>
+__host__ __device__ inline bool arNeuralNetComputeGrad(const float* theta, const float* state, const float* control, float* A,
+                                                       float* B)
+{
+  constexpr int DYNAMICS_DIM = S_DIM - K_DIM;
+  using GRAD = mppi::FNNGradWave<DYNAMICS_DIM + C_DIM, 32, DYNAMICS_DIM>;
+  float s, c;
+  mppi::det::sincos(state[2], &s, &c);
+  A[0 * S_DIM + 2] = -s * state[4] - c * state[5];
+  A[0 * S_DIM + 4] = c;
+  A[0 * S_DIM + 5] = -s;
+  A[1 * S_DIM + 2] = c * state[4] - s * state[5];
+  A[1 * S_DIM + 4] = s;
+  A[1 * S_DIM + 5] = c;
+  A[2 * S_DIM + 6] = -1.0f;  // the pose estimate gives the negative yaw derivative (computeKinematics)
+
+  float in[DYNAMICS_DIM + C_DIM], J[DYNAMICS_DIM][DYNAMICS_DIM + C_DIM];
+#pragma unroll
+  for (int i = 0; i < DYNAMICS_DIM; i++)
+    in[i] = state[K_DIM + i];
+#pragma unroll
+  for (int i = 0; i < C_DIM; i++)
+    in[DYNAMICS_DIM + i] = control[i];
+  GRAD::jacobian(theta, in, J);
+#pragma unroll
+  for (int o = 0; o < DYNAMICS_DIM; o++)
+  {
+#pragma unroll
+    for (int i = 0; i < DYNAMICS_DIM; i++)
+      A[(K_DIM + o) * S_DIM + K_DIM + i] = J[o][i];
+#pragma unroll
+    for (int i = 0; i < C_DIM; i++)
+      B[(K_DIM + o) * C_DIM + i] = J[o][DYNAMICS_DIM + i];
+  }
+  return true;
+}
+/** the blob [W1 | b1 | W2 | b2 | W3 | b3] into the block's LDS, by every thread of the block (a block barrier follows the call) */
+template <int NUM_PARAMS>
+__device__ inline void arNeuralNetStageWeights(const float* __restrict__ theta_d, float* theta_s)
+{
+  const int n = (int)(__builtin_amdgcn_workgroup_size_x() * __builtin_amdgcn_workgroup_size_y() * __builtin_amdgcn_workgroup_size_z());
+  const int tid = (int)((__builtin_amdgcn_workitem_id_z() * __builtin_amdgcn_workgroup_size_y() + __builtin_amdgcn_workitem_id_y()) *
+                            __builtin_amdgcn_workgroup_size_x() +
+                        __builtin_amdgcn_workitem_id_x());
+  for (int i = tid; i < NUM_PARAMS; i += n)
+    theta_s[i] = theta_d[i];
+}
+/**
+ * What a form of the model needs for the wave-per-point computeGrad (plugin/dynamics.hpp: compute_grad_wave), shared by the LDS,
+ * MFMA and wave forms below: each derives from this and says where its blob is, `const float* gradWeights() const`.  No data
+ * members: the forms keep their size and layout.
+ */
+template <class FORM_T, int S_DIM, int C_DIM, int K_DIM>
+struct ARNeuralNetGrad
+{
+  using GRAD_NET = mppi::FNNGradWave<S_DIM - K_DIM + C_DIM, 32, S_DIM - K_DIM>;
+  __host__ __device__ int getGradSharedSizeBytes() const
+  {
+    return ((GRAD_NET::NUM_PARAMS + 3) / 4) * 4 * (int)sizeof(float);
+  }
+  __device__ inline void initializeGrad(float* theta_s) const
+  {
+    arNeuralNetStageWeights<GRAD_NET::NUM_PARAMS>(static_cast<const FORM_T*>(this)->gradWeights(), theta_s);
+  }
+  __host__ __device__ inline bool computeGrad(const float* state, const float* control, float* A, float* B, float* theta_s) const
+  {
+    return arNeuralNetComputeGrad<S_DIM, C_DIM, K_DIM>(theta_s, state, control, A, B);
+  }
+};
+
+template <int S_DIM, int C_DIM, int K_DIM>
+class NeuralNetModel : public Dynamics<NeuralNetModel<S_DIM, C_DIM, K_DIM>, NNDynamicsParams>,
+                       public ARNeuralNetGrad<NeuralNetModel<S_DIM, C_DIM, K_DIM>, S_DIM, C_DIM, K_DIM>
 {
 public:
   using PARENT_CLASS = Dynamics<NeuralNetModel<S_DIM, C_DIM, K_DIM>, NNDynamicsParams>;
@@ -108,6 +186,12 @@ public:
     mppi::lane_sync();
   }
 
+  /** the parameter blob computeGrad's shared region is staged from (ARNeuralNetGrad) */
+  __host__ __device__ const float* gradWeights() const
+  {
+    return helper_.theta_d_;
+  }
+
   mppi::FNNHelper helper_;
 };
 
@@ -121,7 +205,8 @@ template <int S_DIM, int C_DIM, int K_DIM>
 class NeuralNetModelWave;
 
 template <int S_DIM, int C_DIM, int K_DIM>
-class NeuralNetModelMFMA : public Dynamics<NeuralNetModelMFMA<S_DIM, C_DIM, K_DIM>, NNDynamicsParams>
+class NeuralNetModelMFMA : public Dynamics<NeuralNetModelMFMA<S_DIM, C_DIM, K_DIM>, NNDynamicsParams>,
+                           public ARNeuralNetGrad<NeuralNetModelMFMA<S_DIM, C_DIM, K_DIM>, S_DIM, C_DIM, K_DIM>
 {
 public:
   /** no block barrier in the per-step device methods: may run on the role-separated kernels (plugin/parallel_utils.hpp) */
@@ -188,6 +273,12 @@ public:
       state_der[i + (S_DIM - DYNAMICS_DIM)] = out[i];
   }
 
+  /** the parameter blob computeGrad's shared region is staged from (ARNeuralNetGrad) */
+  __host__ __device__ const float* gradWeights() const
+  {
+    return theta_d_;
+  }
+
   const float* theta_d_ = nullptr;
   NET net_;  ///< per-thread weight fragments: the object is passed to the kernel by value, so this lives in VGPRs
 };
@@ -200,7 +291,8 @@ public:
  * rollouts at a time.
  */
 template <int S_DIM, int C_DIM, int K_DIM>
-class NeuralNetModelWave : public Dynamics<NeuralNetModelWave<S_DIM, C_DIM, K_DIM>, NNDynamicsParams>
+class NeuralNetModelWave : public Dynamics<NeuralNetModelWave<S_DIM, C_DIM, K_DIM>, NNDynamicsParams>,
+                           public ARNeuralNetGrad<NeuralNetModelWave<S_DIM, C_DIM, K_DIM>, S_DIM, C_DIM, K_DIM>
 {
 public:
   using PARENT_CLASS = Dynamics<NeuralNetModelWave<S_DIM, C_DIM, K_DIM>, NNDynamicsParams>;
@@ -254,6 +346,12 @@ public:
 #pragma unroll
     for (int i = 0; i < DYNAMICS_DIM; i++)
       state_der[i + (S_DIM - DYNAMICS_DIM)] = out[i];
+  }
+
+  /** the parameter blob computeGrad's shared region is staged from (ARNeuralNetGrad) */
+  __host__ __device__ const float* gradWeights() const
+  {
+    return theta_d_;
   }
 
   const float* theta_d_ = nullptr;

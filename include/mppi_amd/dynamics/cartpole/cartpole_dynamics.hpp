@@ -102,6 +102,44 @@ public:
         (-force * cos_theta - m_p * l_p * SQ(theta_dot) * cos_theta * sin_theta - (m_c + m_p) * gravity_ * sin_theta);
   }
 
+  /**
+   * Continuous-time Jacobians of computeDynamics at (state, control): A[4][4] = d xdot / d x, B[4][1] = d xdot / d u, row-major,
+   * zeroed by the caller (plugin/dynamics.hpp: compute_grad).  Reference: CartpoleDynamics::computeGrad, cartpole_dynamics.cu:10-46.
+   * With s, c of the wrapped angle, w = theta_dot, den = m_c + m_p s^2 and lw2 = l_p w^2:
+   *   d x_dd / d theta      = (m_p c (lw2 + g c) - g m_p s^2) / den - 2 m_p c s (F + m_p s (lw2 + g c)) / den^2
+   *   d theta_dd / d theta  = (F s - g c (m_p + m_c) - l_p m_p w^2 c^2 + l_p m_p w^2 s^2) / (l_p den)
+   *                           + 2 m_p c s (l_p m_p c s w^2 + F c + g s (m_p + m_c)) / (l_p den^2)
+   * The numerator of the second line is a difference of near-equal terms around theta = +-pi/4 and the upright pole; its terms are
+   * added left to right as the reference writes them.  The reference divides the last quotient by (l_p den)^2: one l_p too many,
+   * invisible at its default l_p = 1; here it is the derivative of theta_dd as computeDynamics defines it.
+   */
+  __host__ __device__ inline bool computeGrad(const float* state, const float* control, float* A, float* B) const
+  {
+    float s, c;
+    mppi::det::sincos(angle_utils::normalizeAngleBounded(state[2]), &s, &c);
+    const float w = state[3];
+    const float force = control[0];
+    const float m_c = this->params_.cart_mass;
+    const float m_p = this->params_.pole_mass;
+    const float l_p = this->params_.pole_length;
+    const float g = gravity_;
+    const float den = m_c + m_p * SQ(s);
+    const float swing = l_p * SQ(w) + g * c;  // l_p w^2 + g c
+    const float m_total = m_p + m_c;
+
+    A[0 * 4 + 1] = 1.0f;
+    A[1 * 4 + 2] = (m_p * c * swing - g * m_p * SQ(s)) / den - (2 * m_p * c * s * (force + m_p * s * swing)) / SQ(den);
+    A[1 * 4 + 3] = (2 * l_p * m_p * w * s) / den;
+    A[2 * 4 + 3] = 1.0f;
+    A[3 * 4 + 2] = (force * s - g * c * m_total - l_p * m_p * SQ(w) * SQ(c) + l_p * m_p * SQ(w) * SQ(s)) / (l_p * den) +
+                   (2 * m_p * c * s * (l_p * m_p * c * s * SQ(w) + force * c + g * s * m_total)) / (l_p * SQ(den));
+    A[3 * 4 + 3] = -(2 * m_p * w * c * s) / den;
+
+    B[1] = 1 / den;
+    B[3] = -c / (l_p * den);
+    return true;
+  }
+
   /* Split step (plugin/dynamics.hpp): only (theta, theta_dot) feed back — the cart's x and x_dot integrate values the angle
    * chain produces.  The core advances the angle pair; the completion, on the pipelined kernel's cost wave, rebuilds the cart
    * from sin, cos and the new theta_dot.  Both halves repeat computeDynamics' expressions and updateState's Euler step

@@ -64,6 +64,20 @@ public:
       state_der[HALF + axis] = control[axis];
     }
   }
+
+  /** Jacobians of computeDynamics (di_dynamics.cu:24-34), constant: d p_dot / d v = I and d v_dot / d u = I.  A[4][4], B[4][2]
+   *  row-major, zeroed by the caller (plugin/dynamics.hpp: compute_grad). */
+  __host__ __device__ inline bool computeGrad(const float* state, const float* control, float* A, float* B) const
+  {
+    constexpr int HALF = 2;
+#pragma unroll
+    for (int axis = 0; axis < HALF; axis++)
+    {
+      A[axis * STATE_DIM + HALF + axis] = 1.0f;
+      B[(HALF + axis) * CONTROL_DIM + axis] = 1.0f;
+    }
+    return true;
+  }
 };
 
 #endif

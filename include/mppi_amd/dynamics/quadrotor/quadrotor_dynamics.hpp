@@ -148,6 +148,64 @@ public:
   }
 
   /**
+   * Jacobians of computeDynamics at (state, control): A[13][13], B[13][4] row-major, zeroed by the caller (plugin/dynamics.hpp:
+   * compute_grad).  Reference: QuadrotorDynamics::computeGrad, quadrotor_dynamics.cu:35-68, which fills d x_d / d v, d w_d / d w,
+   * d v_d / d thrust and d w_d / d u, leaves the quaternion columns as TODOs, books d q_d / d w under B, and returns false.
+   * Here every block of the derivative of computeDynamics as written above is filled, so the method returns true:
+   *   d x_d / d v = I
+   *   d v_d / d q = (thrust / mass) d(body z axis) / d q      d v_d / d thrust = (body z axis) / mass
+   *   d q_d / d q, d q_d / d w: omega2edot is bilinear in (w, q), the entries are +-w_i / 2 and +-q_i / 2
+   *   d w_d / d w = -1 / tau                                   d w_d / d u = 1 / tau
+   * (the quaternion is not re-normalised inside computeDynamics, so none of that enters).
+   */
+  __host__ __device__ inline bool computeGrad(const float* state, const float* control, float* A, float* B) const
+  {
+    constexpr int NS = STATE_DIM, NC = CONTROL_DIM;
+    constexpr int P0 = S_INDEX(POS_X), V0 = S_INDEX(VEL_X), Q0 = S_INDEX(QUAT_W), W0 = S_INDEX(ANG_VEL_X);
+    const float* q = state + Q0;
+    const float* w = state + W0;
+    for (int i = 0; i < 3; i++)
+      A[(P0 + i) * NS + V0 + i] = 1.0f;
+
+    const float accel = control[C_INDEX(THRUST)] / this->params_.mass;
+    // rows of d(body z axis) / d(q_w, q_x, q_y, q_z) over 2 (math_utils.hpp: Quat2DCMColumn3)
+    const float dz[3][4] = { { q[2], q[3], q[0], q[1] }, { -q[1], -q[0], q[3], q[2] }, { q[0], -q[1], -q[2], q[3] } };
+    float body_z[3];
+    mppi::math::Quat2DCMColumn3(q, body_z);
+    for (int i = 0; i < 3; i++)
+    {
+      for (int j = 0; j < 4; j++)
+        A[(V0 + i) * NS + Q0 + j] = accel * (2 * dz[i][j]);
+      B[(V0 + i) * NC + C_INDEX(THRUST)] = body_z[i] / this->params_.mass;
+    }
+
+    // q_d = 1/2 q x (0, w): rows by q_d component, columns by q component, then by body rate
+    const float hw[3] = { 0.5f * w[0], 0.5f * w[1], 0.5f * w[2] };
+    const float hq[4] = { 0.5f * q[0], 0.5f * q[1], 0.5f * q[2], 0.5f * q[3] };
+    const float dq_dq[4][4] = { { 0.0f, -hw[0], -hw[1], -hw[2] },
+                                { hw[0], 0.0f, hw[2], -hw[1] },
+                                { hw[1], -hw[2], 0.0f, hw[0] },
+                                { hw[2], hw[1], -hw[0], 0.0f } };
+    const float dq_dw[4][3] = { { -hq[1], -hq[2], -hq[3] }, { hq[0], -hq[3], hq[2] }, { hq[3], hq[0], -hq[1] }, { -hq[2], hq[1], hq[0] } };
+    for (int i = 0; i < 4; i++)
+    {
+      for (int j = 0; j < 4; j++)
+        if (i != j)
+          A[(Q0 + i) * NS + Q0 + j] = dq_dq[i][j];
+      for (int j = 0; j < 3; j++)
+        A[(Q0 + i) * NS + W0 + j] = dq_dw[i][j];
+    }
+
+    const float tau[3] = { this->params_.tau_roll, this->params_.tau_pitch, this->params_.tau_yaw };
+    for (int i = 0; i < 3; i++)
+    {
+      A[(W0 + i) * NS + W0 + i] = -1.0f / tau[i];
+      B[(W0 + i) * NC + C_INDEX(ANG_RATE_X) + i] = 1.0f / tau[i];
+    }
+    return true;
+  }
+
+  /**
    * quadrotor_dynamics.cu:175-188: the Euler step, then q /= |q| * copysign(1, q_w).
    *
    * The reference's device version lets every lane read next_state's quaternion for the norm and the sign while lane 0 may

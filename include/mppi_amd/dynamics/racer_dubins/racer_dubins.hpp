@@ -137,6 +137,62 @@ public:
   }
 
   /**
+   * Jacobians of computeDynamics at (state, control): A[7][7], B[7][2] row-major, zeroed by the caller (plugin/dynamics.hpp:
+   * compute_grad).  The reference declares the method and leaves it empty (`return false`, racer_dubins.cu:36-41); this is the
+   * derivative of the model above, piece by piece:
+   *   brake lag     inside its rate limits  d/d brake = -k_brake, d/d u0 = -k_brake while braking; on a limit both are zero
+   *   longitudinal  d/d v = -c_v, d/d brake = -+c_b by the sign of v, d/d u0 = c_t gear while not braking
+   *   yaw           d/d v = tan(.) / L, d/d steer = v / L (1 + tan^2(.)) / steer_angle_scale
+   *   position      d/d v = (cos yaw, sin yaw), d/d yaw = v (-sin yaw, cos yaw)
+   *   steering lag  inside +-max_steer_rate  d/d steer = -k_steer, d/d u1 = k_cmd k_steer; on the limit zero
+   * At the kinks (u0 = 0, v = 0, a rate exactly on its limit) the one-sided value of the branch computeDynamics takes.  The row of
+   * STEER_ANGLE_RATE stays zero: computeDynamics gives that state no derivative.
+   */
+  __host__ __device__ inline bool computeGrad(const float* state, const float* control, float* A, float* B) const
+  {
+    const RacerDubinsParams& p = this->params_;
+    constexpr int NS = STATE_DIM, NC = CONTROL_DIM;
+    constexpr int V = S_INDEX(VEL_X), YAW = S_INDEX(YAW), PX = S_INDEX(POS_X), PY = S_INDEX(POS_Y), ST = S_INDEX(STEER_ANGLE),
+                  BR = S_INDEX(BRAKE_STATE);
+    constexpr int U_TB = C_INDEX(THROTTLE_BRAKE), U_ST = C_INDEX(STEER_CMD);
+    const float v = state[V], brake = state[BR], steer = state[ST];
+    const float u_tb = control[U_TB], u_steer = control[U_ST];
+    const bool braking = u_tb < 0;
+
+    const float brake_rate = (braking * -u_tb - brake) * p.brake_delay_constant;
+    if (brake_rate > -p.max_brake_rate_neg && brake_rate < p.max_brake_rate_pos)
+    {
+      A[BR * NS + BR] = -p.brake_delay_constant;
+      if (braking)
+        B[BR * NC + U_TB] = -p.brake_delay_constant;
+    }
+
+    A[V * NS + V] = -p.c_v[0];
+    A[V * NS + BR] = p.c_b[0] * (v >= 0 ? -1 : 1);
+    if (!braking)
+      B[V * NC + U_TB] = p.c_t[0] * p.gear_sign;
+
+    const float tan_steer = mppi::det::tan(steer / p.steer_angle_scale);
+    A[YAW * NS + V] = tan_steer / p.wheel_base;
+    A[YAW * NS + ST] = (v / p.wheel_base) * ((1.0f + tan_steer * tan_steer) / p.steer_angle_scale);
+
+    float s_yaw, c_yaw;
+    mppi::det::sincos(angle_utils::normalizeAngle(state[YAW]), &s_yaw, &c_yaw);
+    A[PX * NS + V] = c_yaw;
+    A[PX * NS + YAW] = -(v * s_yaw);
+    A[PY * NS + V] = s_yaw;
+    A[PY * NS + YAW] = v * c_yaw;
+
+    const float steer_rate = (u_steer * p.steer_command_angle_scale - steer) * p.steering_constant;
+    if (steer_rate > -p.max_steer_rate && steer_rate < p.max_steer_rate)
+    {
+      A[ST * NS + ST] = -p.steering_constant;
+      B[ST * NC + U_ST] = p.steer_command_angle_scale * p.steering_constant;
+    }
+    return true;
+  }
+
+  /**
    * HOST: ColoredMPPI's state leash for the RACER models (reference: RacerDubinsImpl::enforceLeash,
    * dynamics/racer_dubins/racer_dubins.cu:176-240): the position error is rotated into the body frame of the true state,
    * clamped there to +-leash[POS_X] / +-leash[POS_Y] and rotated back; the yaw error is the shortest angular distance

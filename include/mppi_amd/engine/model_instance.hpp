@@ -28,6 +28,7 @@
 #include "rollout_pipeline_kernel.hpp"
 #include "rmppi_kernels.hpp"
 #include "rmppi_pipeline_kernel.hpp"
+#include "linearize_kernel.hpp"
 #include "mppi_amd/feedback_controllers/ddp_feedback.hpp"
 #include "mppi_amd/sampling_distributions/colored_noise.hpp"
 
@@ -269,6 +270,18 @@ struct ModelBase
   {
     return 0;
   }
+  /** the Dynamics class declares a device computeGrad (plugin/dynamics.hpp: has_compute_grad) */
+  virtual bool hasComputeGrad() const
+  {
+    return false;
+  }
+  /** A[n][S][S], B[n][S][C] <- the model's Jacobians at the n points x[n][S], u[n][C], all in device memory: one launch of
+   *  kernels::linearizeKernel on `stream` (engine/linearize_kernel.hpp); default: the model declares no computeGrad */
+  virtual mppi_status launchLinearize(const kernels::LinearizeArgs& a, hipStream_t stream, std::string& err)
+  {
+    err = "the model's Dynamics class declares no computeGrad";
+    return MPPI_ERR_UNSUPPORTED;
+  }
 };
 
 /** fingerprint of the structures a model translation unit and libmppi_amd.so exchange (mppi_register_model refuses a
@@ -278,15 +291,16 @@ struct ModelBase
  *  3: rows-in-HBM arguments; 4: release-flag arguments of the finalize kernels (both round 3); 5: supportsStreamedMerge (round 4);
  *  6: FinalizeArgs::phases / carry block of the split hand-over (round 5); 7: undeclaredBarrierFreePlugins; 8: the transposed
  *  record copy (RolloutArgs) and supportsMergeControl / launchMergeControl (both round 6); 9: LaunchRecord,
- *  listReplicatedLaneShapes / supportsRMPPIPipeline (the launch and model introspection of mppi_amd.h); 10: costmapChannels. */
-#define MPPI_ENGINE_ABI_VERSION 10
+ *  listReplicatedLaneShapes / supportsRMPPIPipeline (the launch and model introspection of mppi_amd.h); 10: costmapChannels;
+ *  11: hasComputeGrad / launchLinearize. */
+#define MPPI_ENGINE_ABI_VERSION 11
 
 constexpr int engineAbiFingerprint()
 {
   return MPPI_ENGINE_ABI_VERSION * 1000003 +
          (int)(sizeof(ModelBase) + 131 * sizeof(kernels::RolloutArgs) + 131 * 131 * sizeof(kernels::FinalizeArgs) +
                7 * sizeof(kernels::RMPPIArgs) + 17 * sizeof(kernels::InitEvalArgs) + 31 * sizeof(SamplerLaunchState) +
-               37 * sizeof(kernels::MergeControlArgs));
+               37 * sizeof(kernels::MergeControlArgs) + 41 * sizeof(kernels::LinearizeArgs));
 }
 
 template <class DYN_T, int BY>
@@ -367,6 +381,15 @@ struct has_fnn_helper : std::false_type
 };
 template <class T>
 struct has_fnn_helper<T, std::void_t<decltype(std::declval<T&>().helper_.theta_d_)>> : std::true_type
+{
+};
+template <class T, class = void>
+struct has_grad_weights : std::false_type
+{
+};
+/** dynamics whose computeGrad reads a parameter blob in device memory: `const float* gradWeights() const` */
+template <class T>
+struct has_grad_weights<T, std::void_t<decltype(std::declval<const T&>().gradWeights())>> : std::true_type
 {
 };
 template <class T, class = void>
@@ -1868,6 +1891,47 @@ struct ModelT : ModelBase
       return MPPI_ERR_HIP;
     }
     return MPPI_OK;
+  }
+
+  bool hasComputeGrad() const override
+  {
+    return mppi::has_compute_grad<DYN_T>::value;
+  }
+  mppi_status launchLinearize(const kernels::LinearizeArgs& a, hipStream_t stream, std::string& err) override
+  {
+    if constexpr (mppi::has_compute_grad<DYN_T>::value)
+    {
+      // of the model's bulk data only the network weights enter the Jacobians (a costmap may still be missing): whichever form of
+      // a model is the DYN_T here says where they are with gradWeights()
+      if constexpr (has_grad_weights<DYN_T>::value)
+        if (!dyn.gradWeights())
+        {
+          err = "model needs the 'dynamics_weights' blob (mppi_set_model_blob) before it can be linearised";
+          return MPPI_ERR_STATE;
+        }
+      if (a.n < 1 || !a.x_d || !a.u_d || !a.A_d || !a.B_d)
+      {
+        err = "linearizeKernel: n >= 1 points and four device pointers";
+        return MPPI_ERR_INVALID_ARG;
+      }
+      const size_t smem = kernels::linearizeSharedBytes(dyn);
+      auto kfn = kernels::linearizeKernel<DYN_T>;
+      hipError_t e = ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
+      if (e == hipSuccess)
+      {
+        constexpr int P = kernels::linearizeBlockPoints<DYN_T>();
+        hipLaunchKernelGGL(kfn, dim3((a.n + P - 1) / P), dim3(64 * kernels::linearizeBlockWaves<DYN_T>(), 1, 1), smem, stream, dyn,
+                           a, kernels::linearizeModelSharedBytes(dyn));
+        e = hipGetLastError();
+      }
+      if (e != hipSuccess)
+      {
+        err = std::string("linearizeKernel launch: ") + hipGetErrorString(e);
+        return MPPI_ERR_HIP;
+      }
+      return MPPI_OK;
+    }
+    return ModelBase::launchLinearize(a, stream, err);
   }
 };
 

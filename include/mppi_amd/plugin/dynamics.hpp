@@ -323,6 +323,49 @@ template <class T>
 struct split_step<T, std::void_t<typename T::SPLIT_STEP_CLASS>> : std::is_same<typename T::SPLIT_STEP_CLASS, T>
 {
 };
+
+/**
+ * Linearisation (opt-in): the continuous-time Jacobians of the model at one point, the device form of the reference's
+ * Dynamics::computeGrad(state, control, A, B) (dynamics/dynamics.cuh:239; called once per time step by its DDP feedback).  A
+ * plugin declares one of
+ *
+ *   __device__ bool computeGrad(const float* x, const float* u, float* A, float* B);
+ *       one lane evaluates one point
+ *   __device__ bool computeGrad(const float* x, const float* u, float* A, float* B, float* theta_s);
+ *       one WAVE evaluates one point (all 64 lanes make the call with the same arguments and write the same values), with a
+ *       block-shared region theta_s the model sizes and fills itself:
+ *         __host__ __device__ int getGradSharedSizeBytes() const;
+ *         __device__ void initializeGrad(float* theta_s) const;      every thread of the block calls it, a block barrier follows
+ *
+ * A[S][S] row-major with A[i][j] = d xdot_i / d x_j, B[S][C] row-major with B[i][j] = d xdot_i / d u_j; the caller forms
+ * I + A dt.  Both arrive zeroed (engine/linearize_kernel.hpp clears them), so the method writes only the entries its formula sets.
+ * The method holds no block barrier.  The value it returns is the reference's (`false`: no analytic gradient); the engine does not
+ * consult it — a class without a gradient declares nothing, compiles exactly as before, and is reported as unsupported at run time
+ * (mppi_has_compute_grad).  Detected as MPPI_BARRIER_FREE_STEP is: by what the class itself says.
+ */
+template <class T, class = void>
+struct compute_grad_lane : std::false_type
+{
+};
+template <class T>
+struct compute_grad_lane<T, std::void_t<decltype(std::declval<T&>().computeGrad((const float*)nullptr, (const float*)nullptr,
+                                                                               (float*)nullptr, (float*)nullptr))>> : std::true_type
+{
+};
+template <class T, class = void>
+struct compute_grad_wave : std::false_type
+{
+};
+template <class T>
+struct compute_grad_wave<T, std::void_t<decltype(std::declval<T&>().computeGrad((const float*)nullptr, (const float*)nullptr,
+                                                                               (float*)nullptr, (float*)nullptr, (float*)nullptr))>>
+  : std::true_type
+{
+};
+template <class T>
+struct has_compute_grad : std::integral_constant<bool, compute_grad_lane<T>::value || compute_grad_wave<T>::value>
+{
+};
 }  // namespace mppi
 
 #endif

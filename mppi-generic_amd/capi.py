@@ -140,6 +140,9 @@ SIGNATURES = {
     "mppi_get_output_seq": (C.c_int, [H, _f32p]),
     "mppi_get_nominal_control_seq": (C.c_int, [H, _f32p]),
     "mppi_get_nominal_state_seq": (C.c_int, [H, _f32p]),
+    "mppi_has_compute_grad": (C.c_int, [H]),
+    "mppi_linearize": (C.c_int, [H, _f32p, _f32p, C.c_int, _f32p, _f32p]),
+    "mppi_linearize_trajectory": (C.c_int, [H, C.c_int, _f32p, _f32p]),
     "mppi_slide": (C.c_int, [H, C.c_int]),
     "mppi_get_costs": (C.c_int, [H, _f32p]),
     "mppi_get_stats": (C.c_int, [H, C.POINTER(MppiStats)]),

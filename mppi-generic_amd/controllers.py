@@ -623,6 +623,32 @@ class MPPIController:
         self._check(self._lib.mppi_get_state_seq(self._h, x))
         return x
 
+    def hasComputeGrad(self):
+        """does the model's Dynamics class declare a device computeGrad (mppi_has_compute_grad)"""
+        return bool(self._lib.mppi_has_compute_grad(self._h))
+
+    def computeGrad(self, states, controls):
+        """Dynamics::computeGrad at n points: states (n, S) and controls (n, C) (one point may be given flat) -> the
+        continuous-time Jacobians A (n, S, S) = d xdot / d x and B (n, S, C) = d xdot / d u, float32 (mppi_linearize)"""
+        x = np.ascontiguousarray(states, np.float32).reshape(-1, self.STATE_DIM)
+        u = np.ascontiguousarray(controls, np.float32).reshape(-1, self.CONTROL_DIM)
+        if x.shape[0] != u.shape[0]:
+            raise MPPIError(MPPI_ERR_INVALID_ARG, "computeGrad: %d states, %d controls" % (x.shape[0], u.shape[0]))
+        n = x.shape[0]
+        A = np.empty((n, self.STATE_DIM, self.STATE_DIM), np.float32)
+        B = np.empty((n, self.STATE_DIM, self.CONTROL_DIM), np.float32)
+        self._check(self._lib.mppi_linearize(self._h, x.reshape(-1), u.reshape(-1), n, A.reshape(-1), B.reshape(-1)))
+        return A, B
+
+    def computeGradTrajectory(self, system=0):
+        """A (T, S, S), B (T, S, C) along the result of the last computeControl, read on the device
+        (mppi_linearize_trajectory): system 0 the sequences getTargetStateSeq / getControlSeq return, system 1 the nominal
+        ones of a Tube / Robust controller"""
+        A = np.empty((self.num_timesteps, self.STATE_DIM, self.STATE_DIM), np.float32)
+        B = np.empty((self.num_timesteps, self.STATE_DIM, self.CONTROL_DIM), np.float32)
+        self._check(self._lib.mppi_linearize_trajectory(self._h, system, A.reshape(-1), B.reshape(-1)))
+        return A, B
+
     def getTargetOutputSeq(self):
         y = np.empty((self.num_timesteps, self.OUTPUT_DIM), np.float32)
         self._check(self._lib.mppi_get_output_seq(self._h, y))

@@ -822,11 +822,96 @@ mppi_status mppi_compute_control(mppi_handle h, const float* x0, int stride)
   RoctxRange range("mppi:compute_control");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   h->last_stride = stride;
-  if (h->cfg.controller == MPPI_CONTROLLER_TUBE)
-    return computeControlTube(h, x0, stride);
-  if (h->cfg.controller == MPPI_CONTROLLER_ROBUST)
-    return computeControlRobust(h, x0, stride);
-  return computeControlVanilla(h, x0, stride);
+  const mppi_status st = h->cfg.controller == MPPI_CONTROLLER_TUBE   ? computeControlTube(h, x0, stride) :
+                         h->cfg.controller == MPPI_CONTROLLER_ROBUST ? computeControlRobust(h, x0, stride) :
+                                                                       computeControlVanilla(h, x0, stride);
+  if (st == MPPI_OK)
+    h->have_result = true;
+  return st;
+}
+
+/* ---------------------------------------------------------------- linearisation ---------------------------------- */
+int mppi_has_compute_grad(mppi_handle h)
+{
+  return h && h->model->hasComputeGrad() ? 1 : 0;
+}
+
+/** the Jacobians at the n points x_d[n][S], u_d[n][C] (device memory) into the caller's host arrays: one launch behind whatever
+ *  the stream holds, two copies back, one synchronisation */
+static mppi_status linearizeOnDevice(mppi_handle h, const float* x_d, const float* u_d, int n, float* A_out, float* B_out)
+{
+  const size_t nA = (size_t)n * h->S * h->S, nB = (size_t)n * h->S * h->C;
+  if (h->lin_out_d.size() < nA + nB)
+  {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));  // an earlier launch may still write the old buffer
+    HIP_TRY(h, h->lin_out_d.alloc(nA + nB));
+  }
+  kernels::LinearizeArgs a{};
+  a.x_d = x_d;
+  a.u_d = u_d;
+  a.A_d = h->lin_out_d;
+  a.B_d = h->lin_out_d + nA;
+  a.n = n;
+  std::string err;
+  const mppi_status st = h->model->launchLinearize(a, h->stream, err);
+  if (st != MPPI_OK)
+    return fail(h, st, err);
+  HIP_TRY(h, hipMemcpyAsync(A_out, a.A_d, sizeof(float) * nA, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(B_out, a.B_d, sizeof(float) * nB, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MPPI_OK;
+}
+
+mppi_status mppi_linearize(mppi_handle h, const float* x, const float* u, int n, float* A_out, float* B_out)
+{
+  CHECK_HANDLE(h);
+  if (!x || !u || !A_out || !B_out)
+    return fail(h, MPPI_ERR_INVALID_ARG, "mppi_linearize: null pointer");
+  if (n <= 0)
+    return fail(h, MPPI_ERR_INVALID_ARG, "mppi_linearize: n must be at least 1");
+  if (!h->model->hasComputeGrad())
+    return fail(h, MPPI_ERR_UNSUPPORTED, "mppi_linearize: the Dynamics class of model '" + h->model_name + "' declares no computeGrad");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  const size_t nx = (size_t)n * h->S, nu = (size_t)n * h->C;
+  if (h->lin_in_d.size() < nx + nu)
+  {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, h->lin_in_d.alloc(nx + nu));
+  }
+  HIP_TRY(h, hipMemcpyAsync(h->lin_in_d, x, sizeof(float) * nx, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->lin_in_d + nx, u, sizeof(float) * nu, hipMemcpyHostToDevice, h->stream));
+  return linearizeOnDevice(h, h->lin_in_d, h->lin_in_d + nx, n, A_out, B_out);
+}
+
+mppi_status mppi_linearize_trajectory(mppi_handle h, int system, float* A_out, float* B_out)
+{
+  CHECK_HANDLE(h);  // (split hand-over: behind the trajectory phase that writes the state sequence)
+  if (!A_out || !B_out)
+    return fail(h, MPPI_ERR_INVALID_ARG, "mppi_linearize_trajectory: null pointer");
+  if (!h->model->hasComputeGrad())
+    return fail(h, MPPI_ERR_UNSUPPORTED,
+                "mppi_linearize_trajectory: the Dynamics class of model '" + h->model_name + "' declares no computeGrad");
+  if (system != 0 && !(system == 1 && h->D == 2))
+    return fail(h, MPPI_ERR_INVALID_ARG, "mppi_linearize_trajectory: system 0, or 1 (the nominal system) on a Tube / Robust handle");
+  if (!h->have_result)
+    return fail(h, MPPI_ERR_STATE, "mppi_linearize_trajectory: no mppi_compute_control has run on this handle yet");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  // which system of the last finalize pass holds the sequence a getter reports: through the system table, as the getters do
+  const std::vector<float>* xs = system == 0 ? h->sys.state[0] : &h->nominal_state_h;
+  const std::vector<float>* us = system == 0 ? &h->control_h : &h->nominal_control_h;
+  int zx = 0, zu = 0;
+  for (int z = 0; z < h->D; z++)
+  {
+    if (h->sys.state[z] == xs)
+      zx = z;
+    if (h->sys.control[z] == us)
+      zu = z;
+  }
+  const int T = h->cfg.num_timesteps;
+  float* base = h->results_in_io ? h->io_out_h.dev() : h->out_block_d.get();
+  const float* x_d = outSlice(base, h->out.state) + (size_t)zx * T * h->S;
+  const float* u_d = outSlice(base, h->out.control) + (size_t)zu * h->TC;
+  return linearizeOnDevice(h, x_d, u_d, T, A_out, B_out);
 }
 
 mppi_status mppi_get_control_seq(mppi_handle h, float* u)

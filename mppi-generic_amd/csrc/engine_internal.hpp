@@ -226,6 +226,9 @@ struct mppi_handle_s
   HipBuffer<float> step_pin_h;     // [S + C] host memory mapped into the device: [x | u] of a single model step
   unsigned step_seq = 0;           // hand-over counter of the model-step flag (io_flags[8])
   size_t in_floats = 0, out_floats = 0;
+  bool have_result = false;        // a mppi_compute_control has succeeded: the out block / outbox holds its sequences
+  HipBuffer<float> lin_in_d;       // mppi_linearize: the caller's points [n][S] | [n][C]
+  HipBuffer<float> lin_out_d;      // mppi_linearize / mppi_linearize_trajectory: A [n][S][S] | B [n][S][C]
   bool out_pin_fresh = false;      // out_pin_h holds the results (incl. stats) of the last finalize pass; reset by launches
   bool stats_h_fresh = false;      // stats_h IS the statistics of the last merge (parsed at a low-latency hand-over); reset by launches
   HipBuffer<float> step_x_d;       // [S + C]

@@ -147,3 +147,29 @@ if "autorally-robust" in which:
         us = (time.perf_counter() - t0) / 30 * 1e6
         print("%-10s K=%d T=%d Robust computeControl %.1f us (%s)" % (name, cfg["K"], cfg["T"], us, eng.getLaunchInfo()["family"]), flush=True)
         eng.close()
+if "linearize" in which:
+    # mppi_linearize_trajectory next to the same handle's computeControl: wall time of the whole call (launch, two copies back,
+    # one synchronisation), median and spread over repeated calls after warm-up.  5000 calls each: a timed window of 0.2 - 1.2 s,
+    # so that clock ramp and scheduler noise are a small part of it.  The kernel's own time is not in these figures; take it
+    # from a kernel trace of this mode, in a run of its own.
+    import time  # noqa: E402
+    for name, cfg in (("cartpole", cartpole_cfg(K=16384, T=100)), ("autorally", autorally_cfg(K=16384, T=150, lambda_=1.0))):
+        eng = make_engine(cfg)
+        for _ in range(200):
+            eng.computeControl(cfg["x0"], 1)
+            eng.computeGradTrajectory()
+
+        def timed(fn, n=5000):
+            t = []
+            for _ in range(n):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e6)
+            return np.percentile(t, [50, 10, 90])
+
+        cc = timed(lambda: eng.computeControl(cfg["x0"], 1))
+        eng.getTargetStateSeq()
+        lin = timed(eng.computeGradTrajectory)
+        print("%-10s K=%d T=%d computeControl %.1f us (p10 %.1f, p90 %.1f); linearize_trajectory %.1f us (p10 %.1f, p90 %.1f)"
+              % ((name, cfg["K"], cfg["T"]) + tuple(cc) + tuple(lin)), flush=True)
+        eng.close()
