@@ -8,7 +8,7 @@
  * .y the track position, .z the speed map and .w the heading.  Here it is a plain `float[height][width][4]` array in HBM, 16-byte
  * aligned, one texel = one 16-byte load; the texel is chosen by the rule ARStandardCost::queryTextureTransformed states
  * (floor(u * width), floor(v * height), clamped, NaN -> 0).  COSTMAP_CHANNELS tells the engine which "costmap" blob the class
- * takes: {height, width, 4}, interleaved texels (engine/model_instance.hpp).
+ * takes: {height, width, 4}, interleaved texels (engine/model_traits.hpp: costmap_channels; engine/model_blobs.hpp: checkMapDims).
  *
  * The DEVICE branch is restated (the project's rule), on the host as on the device.  Kept as the reference has them:
  *   - the double literals of getStabilizingCost promote to fp64: `slip >= 0.75 * max_slip_ang` compares in double, and the ramp

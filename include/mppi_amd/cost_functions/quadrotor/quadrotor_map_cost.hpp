@@ -145,7 +145,7 @@ public:
   static constexpr float MAX_COST_VALUE = 1e16;
 
   /** the track map: one texture, one channel; the engine fills it from the "costmap" / "costmap_transform" blobs
-   *  (engine/model_instance.hpp).  Not in use (checkTextureUse(0) false) means the map term is 0. */
+   *  (engine/model_blobs.hpp: bindMap, setMapFrame).  Not in use (checkTextureUse(0) false) means the map term is 0. */
   TexHelper tex_helper_;
 
   QuadrotorMapCost(hipStream_t stream = nullptr)

@@ -5,6 +5,9 @@
  * interface — the role played in the reference by its explicit instantiations
  * (reference: include/mppi/instantiations/cartpole_mppi/cartpole_mppi.cuh, src/controllers/cartpole/cartpole_mppi.cu:30-42).
  * Block shapes are compile-time (see rollout_kernel.hpp); each model lists the shapes it is instantiated for.
+ *
+ * The pieces around ModelT: model_base.hpp (ModelBase and the ABI fingerprint), model_traits.hpp (what a plugin class has),
+ * model_launch.hpp (the one checked launch path), model_blobs.hpp (the bulk-data checks and uploads).
  */
 #ifndef MPPI_AMD_MODEL_INSTANCE_HPP_
 #define MPPI_AMD_MODEL_INSTANCE_HPP_
@@ -13,8 +16,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
-#include <map>
-#include <mutex>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -23,6 +24,10 @@
 #include "mppi_amd.h"
 #include "hip_owned.hpp"
 #include "kernarg_view.hpp"
+#include "model_base.hpp"
+#include "model_traits.hpp"
+#include "model_launch.hpp"
+#include "model_blobs.hpp"
 #include "rollout_kernel.hpp"
 #include "finalize_kernel.hpp"
 #include "rollout_pipeline_kernel.hpp"
@@ -32,277 +37,10 @@
 #include "mppi_amd/feedback_controllers/ddp_feedback.hpp"
 #include "mppi_amd/sampling_distributions/colored_noise.hpp"
 
-/**
- * hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, raised only when a launch needs more than was granted before: the
- * attribute call is a runtime round trip (function lookup, locks) that every rollout launch of a > 48 KiB block paid in front of
- * its dispatch — on the host's critical path of mppi_compute_control, where the first launch's enqueue time decides when the
- * device starts.  The grant is per (device, kernel) and monotonic, so handles sharing a kernel on a device never lower each
- * other's limit.
- */
-inline hipError_t ensureDynamicLds(const void* fn, size_t smem)
-{
-  if (smem <= 48 * 1024)
-    return hipSuccess;
-  static std::mutex mu;
-  static std::map<std::pair<int, const void*>, size_t> granted;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lock(mu);
-  size_t& g = granted[std::make_pair(dev, fn)];
-  if (smem <= g)
-    return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e == hipSuccess)
-    g = smem;
-  return e;
-}
-
 namespace mppi
 {
 namespace engine
 {
-constexpr size_t MAX_LDS_BYTES = 160 * 1024;  // gfx950: 160 KiB per CU, one workgroup may take all of it
-
-template <int X, int Y, int Z>
-struct Shape
-{
-};
-template <class... S>
-struct Shapes
-{
-};
-
-/** everything the sampler needs to know for one launch (the engine refreshes it before every launch) */
-struct SamplerLaunchState
-{
-  int num_rollouts_local, num_rollouts_global, rollout_offset;
-  int num_timesteps, num_distributions;
-  float* control_means_d;
-  const float* eps_d;  // nullptr => Philox
-  float* control_samples_d;
-  uint64_t seed;
-  uint32_t generation;
-  int iteration;  // opt_iter for std_dev_decay
-  int optimization_stride;
-  int independent_noise;  // != 0: use_same_noise_for_all_distributions off (every distribution its own stream / eps slab)
-};
-
-/** what the most recent rollout launch of a model object ran (mppi_get_launch_info): written by the dispatch itself, at the
- *  point where it has picked the kernel and the launch went out, so the query never recomputes the choice */
-struct LaunchRecord
-{
-  int family = MPPI_FAMILY_NONE;  ///< mppi_kernel_family
-  int bx = 0, by = 0, bz = 0;     ///< the registered block shape the launch was dispatched for
-  bool rows_in_hbm = false;       ///< the sampler's rows in HBM (setGlobalRows)
-  bool streamed_merge = false;    ///< the sampler waves merged the previous launch's block records (STREAM_MERGE form)
-};
-
-struct ModelBase
-{
-  int S = 0, C = 0, O = 0;
-  int default_bx = 64, default_by = 1;
-  LaunchRecord last_launch;
-  virtual ~ModelBase() = default;
-  virtual mppi_status setDynamicsParams(const void* pod, size_t n) = 0;
-  virtual mppi_status setCostParams(const void* pod, size_t n) = 0;
-  virtual void setControlRanges(const float* lo_hi) = 0;
-  virtual void setControlDeadband(const float* db) = 0;
-  virtual void getZeroControl(float* out) const = 0;
-  /** Dynamics::enforceLeash (dynamics/dynamics.cuh:448-466), host: per state dimension, the nominal state if it is within
-   *  the leash of the true state, else the true state moved towards it by the leash.  A plugin with an enforceLeash() host
-   *  method of its own (RacerDubins: position leash in the body frame, racer_dubins.cu:177-230) overrides it. */
-  virtual void hostEnforceLeash(const float* state_true, const float* state_nominal, const float* leash, float* out) const
-  {
-    for (int i = 0; i < S; i++)
-    {
-      const float diff = fabsf(state_nominal[i] - state_true[i]);
-      if (leash[i] < diff)
-        out[i] = state_true[i] + fminf(fmaxf(state_nominal[i] - state_true[i], -leash[i]), leash[i]);
-      else
-        out[i] = state_nominal[i];
-    }
-  }
-  /** the base enforceConstraints rule on the host (dynamics.cu:97-116); false: the plugin overrides it, run the device code */
-  virtual bool hostEnforceConstraints(float* u) const = 0;
-  virtual void setSamplerParams(const mppi_gaussian_params* p, int D) = 0;
-  /** bulk data (NN weights, costmap); default: the model has none */
-  virtual mppi_status setBlob(const std::string& name, const float* data, size_t count, const int* dims, int ndims,
-                              hipStream_t stream, std::string& err)
-  {
-    err = "model has no blob named '" + name + "'";
-    return MPPI_ERR_INVALID_ARG;
-  }
-  /** LSTMHelper::copyHiddenCellToDevice (lstm_helper.cu:480-500): new initial hidden / cell state of the rollouts' LSTM,
-   *  on the engine's stream without re-uploading the weights; default: the model has no LSTM */
-  virtual mppi_status setLSTMInitialState(const float* hidden, const float* cell, hipStream_t stream, std::string& err)
-  {
-    err = "model has no LSTM";
-    return MPPI_ERR_INVALID_ARG;
-  }
-  /** time_specific_std_dev: sigma[D][T][C] table in device memory (owned by the engine), nullptr switches it off */
-  virtual void setTimeSpecificStdDev(const float* table_d) = 0;
-  /** colored-noise sampler parameters (ColoredNoiseParamsImpl, colored_noise.cuh:45-73); default: Gaussian sampler */
-  virtual mppi_status setColoredNoiseParams(const float* exponents, float offset_decay_rate, float fmin)
-  {
-    return MPPI_ERR_STATE;
-  }
-  /** floats of injected noise per rollout: T*C time-domain eps, or C*(2T+2) spectrum entries for colored noise */
-  virtual size_t noiseFloatsPerRollout(int T) const = 0;
-  /** the sampled noise eps[K_local][T][C] the next launch would use, written to out_d (generator parity tests) */
-  virtual mppi_status launchNoiseDump(const SamplerLaunchState& s, float* out_d, hipStream_t stream, std::string& err) = 0;
-  /* ---- Robust MPPI (rmppi_kernels.hpp); default: the model is not instantiated for it ---- */
-  virtual bool supportsRMPPI() const
-  {
-    return false;
-  }
-  /** DDP feedback gains [T][S][C] (ddp.cuh:18-60) -> device; accumulate_all_states: see ddp_feedback.hpp */
-  virtual mppi_status setFeedbackGains(const float* gains, int T, bool accumulate_all_states, hipStream_t stream,
-                                       std::string& err)
-  {
-    err = "model is not instantiated for Robust MPPI";
-    return MPPI_ERR_UNSUPPORTED;
-  }
-  virtual mppi_status launchInitEval(bool pipeline, const kernels::InitEvalArgs& a, const SamplerLaunchState& s,
-                                     hipStream_t stream, std::string& err)
-  {
-    err = "model is not instantiated for Robust MPPI";
-    return MPPI_ERR_UNSUPPORTED;
-  }
-  /** pipeline: the role-pipelined kernel (rmppi_pipeline_kernel.hpp) when the model has one and its replicated-lane form is
-   *  usable with the loaded networks, else rolloutRMPPIKernel */
-  virtual mppi_status launchRMPPI(int bx, bool pipeline, const kernels::RMPPIArgs& a, const SamplerLaunchState& s,
-                                  hipStream_t stream, std::string& err)
-  {
-    err = "model is not instantiated for Robust MPPI";
-    return MPPI_ERR_UNSUPPORTED;
-  }
-  virtual size_t rmppiSharedBytes(int bx, int T)
-  {
-    return 0;
-  }
-  /** LDS request of the role-pipelined Robust MPPI kernel (64 rollouts x 2 systems per block); 0: the model has none, its
-   *  replicated-lane form does not take the loaded networks, or not even the shortest rings fit */
-  virtual size_t rmppiPipelineSharedBytes(int T)
-  {
-    return 0;
-  }
-  /** world -> texture transform of a costmap cost (ARStandardCost::updateTransform, ar_standard_cost.cu:132-137) */
-  virtual mppi_status setCostmapTransform(const float* r_c1, const float* r_c2, const float* trs)
-  {
-    return MPPI_ERR_INVALID_ARG;
-  }
-  virtual bool supportsShape(int bx, int by, int bz) const = 0;
-  /** role-pipelined variant (rollout_pipeline_kernel.hpp) available for this model? */
-  virtual bool supportsPipeline() const
-  {
-    return false;
-  }
-  /** "" when every plugin class the model's ROLE-SEPARATED kernels would run declares MPPI_BARRIER_FREE_STEP
-   *  (plugin/parallel_utils.hpp: barrier_free_step) — or when the model has no such kernels; otherwise the names the
-   *  declaration is missing from.  mppi_create refuses a model with a non-empty answer: a block barrier inside a per-step
-   *  method would hang those kernels (only the wave whose role it is calls the method). */
-  virtual std::string undeclaredBarrierFreePlugins() const
-  {
-    return std::string();
-  }
-  /** rolloutPipelineKernel's STREAM_MERGE form exists: one system, Gaussian sampler drawing in the loop */
-  virtual bool supportsStreamedMerge() const
-  {
-    return false;
-  }
-  /** role-pipelined variant with the two systems of Tube-MPPI folded into the lanes of a wave, shape (32, 1, 2) */
-  virtual bool supportsPipelineFold(int bx, int by, int bz) const
-  {
-    return false;
-  }
-  /** role-pipelined variant for replicated-lane (MFMA) dynamics, shape (64, REP, 1) */
-  virtual bool supportsPipelineRep(int bx, int by, int bz) const
-  {
-    return false;
-  }
-  /** the shape is a replicated-lane one that the model's present data rule out (networks of another shape than the
-   *  replicated-lane form is compiled for) */
-  virtual bool fastShapeRefused(int bx, int by, int bz) const
-  {
-    return false;
-  }
-  virtual size_t rolloutSharedBytes(int bx, int by, int bz, int T, int D, bool pipeline) = 0;
-  /** floats the sampler needs for the sample rows of `blocks` blocks of `slots` rollout slots in HBM (long horizons), 0: the
-   *  sampler keeps its rows in LDS only; setGlobalRows(ptr) switches the fused kernel over (nullptr: back to LDS) */
-  virtual size_t globalRowsFloats(int blocks, int slots, int T) const
-  {
-    return 0;
-  }
-  virtual void setGlobalRows(float* rows_d)
-  {
-  }
-  /** every registered block shape as (bx, by, bz) triples, flattened */
-  virtual void listShapes(std::vector<int>& out) const = 0;
-  virtual mppi_status launchRollout(int bx, int by, int bz, bool pipeline, const kernels::RolloutArgs& args,
-                                    const SamplerLaunchState& s, hipStream_t stream, std::string& err) = 0;
-  virtual mppi_status launchFinalize(int D, const kernels::FinalizeArgs& a, hipStream_t stream, std::string& err) = 0;
-  /** the control phase of a split hand-over that merges the last launch's block records itself (kernels::mergeControlKernel):
-   *  one system on the plain one-wave finalize form, control sequence in LDS */
-  virtual bool supportsMergeControl(int num_timesteps) const
-  {
-    return false;
-  }
-  virtual mppi_status launchMergeControl(const kernels::FinalizeArgs& a, const kernels::MergeControlArgs& m, hipStream_t stream,
-                                         std::string& err)
-  {
-    err = "model has no merging control phase";
-    return MPPI_ERR_LAUNCH_SHAPE;
-  }
-  /** x <- one model step (optionally after enforceConstraints on u), one block (1, by, 1) */
-  virtual mppi_status launchModelStep(float* x_d, float* u_d, float dt, int enforce, hipStream_t stream,
-                                      std::string& err) = 0;
-  /** the replicated-lane (MFMA / four-lane) block shapes among listShapes(), as (bx, by, bz) triples, flattened */
-  virtual void listReplicatedLaneShapes(std::vector<int>& out) const
-  {
-  }
-  /** the role-pipelined Robust MPPI kernel (rmppi_pipeline_kernel.hpp) is instantiated for this model */
-  virtual bool supportsRMPPIPipeline() const
-  {
-    return false;
-  }
-  /** channels of the "costmap" blob of a cost with costmap_d_: 1 {height, width}, 4 {height, width, 4}; 0: the cost has none */
-  virtual int costmapChannels() const
-  {
-    return 0;
-  }
-  /** the Dynamics class declares a device computeGrad (plugin/dynamics.hpp: has_compute_grad) */
-  virtual bool hasComputeGrad() const
-  {
-    return false;
-  }
-  /** A[n][S][S], B[n][S][C] <- the model's Jacobians at the n points x[n][S], u[n][C], all in device memory: one launch of
-   *  kernels::linearizeKernel on `stream` (engine/linearize_kernel.hpp); default: the model declares no computeGrad */
-  virtual mppi_status launchLinearize(const kernels::LinearizeArgs& a, hipStream_t stream, std::string& err)
-  {
-    err = "the model's Dynamics class declares no computeGrad";
-    return MPPI_ERR_UNSUPPORTED;
-  }
-};
-
-/** fingerprint of the structures a model translation unit and libmppi_amd.so exchange (mppi_register_model refuses a
- *  plugin built against other headers: its kernels would read the argument blocks with the wrong layout) */
-/** bumped BY HAND whenever ModelBase's virtual methods are added, removed or reordered or a field of an argument struct is
- *  swapped at equal size — changes sizeof() cannot see (a stale plugin would dispatch to the wrong vtable slot).
- *  3: rows-in-HBM arguments; 4: release-flag arguments of the finalize kernels (both round 3); 5: supportsStreamedMerge (round 4);
- *  6: FinalizeArgs::phases / carry block of the split hand-over (round 5); 7: undeclaredBarrierFreePlugins; 8: the transposed
- *  record copy (RolloutArgs) and supportsMergeControl / launchMergeControl (both round 6); 9: LaunchRecord,
- *  listReplicatedLaneShapes / supportsRMPPIPipeline (the launch and model introspection of mppi_amd.h); 10: costmapChannels;
- *  11: hasComputeGrad / launchLinearize. */
-#define MPPI_ENGINE_ABI_VERSION 11
-
-constexpr int engineAbiFingerprint()
-{
-  return MPPI_ENGINE_ABI_VERSION * 1000003 +
-         (int)(sizeof(ModelBase) + 131 * sizeof(kernels::RolloutArgs) + 131 * 131 * sizeof(kernels::FinalizeArgs) +
-               7 * sizeof(kernels::RMPPIArgs) + 17 * sizeof(kernels::InitEvalArgs) + 31 * sizeof(SamplerLaunchState) +
-               37 * sizeof(kernels::MergeControlArgs) + 41 * sizeof(kernels::LinearizeArgs));
-}
-
 template <class DYN_T, int BY>
 __global__ void __launch_bounds__(BY) modelStepKernel(DYN_T dynamics_obj, float* x_d, float* u_d, float dt, int enforce)
 {
@@ -374,126 +112,6 @@ __global__ void __launch_bounds__(64) noiseDumpKernel(SAMPLING_T sampling_obj, f
 }  // namespace kernels
 namespace engine
 {
-/* detection of optional plugin members */
-template <class T, class = void>
-struct has_fnn_helper : std::false_type
-{
-};
-template <class T>
-struct has_fnn_helper<T, std::void_t<decltype(std::declval<T&>().helper_.theta_d_)>> : std::true_type
-{
-};
-template <class T, class = void>
-struct has_grad_weights : std::false_type
-{
-};
-/** dynamics whose computeGrad reads a parameter blob in device memory: `const float* gradWeights() const` */
-template <class T>
-struct has_grad_weights<T, std::void_t<decltype(std::declval<const T&>().gradWeights())>> : std::true_type
-{
-};
-template <class T, class = void>
-struct has_lstm_helper : std::false_type
-{
-};
-template <class T>
-struct has_lstm_helper<T, std::void_t<decltype(std::declval<T&>().lstm_.weights_d_)>> : std::true_type
-{
-};
-template <class T, class = void>
-struct has_host_leash : std::false_type
-{
-};
-template <class T>
-struct has_host_leash<T, std::void_t<decltype(std::declval<const T&>().enforceLeash((const float*)nullptr, (const float*)nullptr,
-                                                                                     (const float*)nullptr, (float*)nullptr))>>
-  : std::true_type
-{
-};
-template <class T, class = void>
-struct has_lstm_structure : std::false_type
-{
-};
-/** dynamics whose LSTM shape can be changed at run time (setLSTMStructure, the "lstm_structure" blob) */
-template <class T>
-struct has_lstm_structure<T, std::void_t<decltype(std::declval<T&>().setLSTMStructure((const int*)nullptr, 0))>> : std::true_type
-{
-};
-/** a replicated-lane form that names a sibling made for ONE rollout per wave (`using FINALIZE_FORM = ...`) */
-template <class T, class = void>
-struct has_finalize_form : std::false_type
-{
-};
-template <class T>
-struct has_finalize_form<T, std::void_t<typename T::FINALIZE_FORM>> : std::true_type
-{
-};
-template <class T, class = void>
-struct has_register_form : std::false_type
-{
-};
-/** dynamics whose replicated-lane (FAST) variant exists for one network shape only (`register_form_`) */
-template <class T>
-struct has_register_form<T, std::void_t<decltype(std::declval<T&>().register_form_)>> : std::true_type
-{
-};
-template <class T, class = void>
-struct has_elevation_map : std::false_type
-{
-};
-/** dynamics with a TwoDTextureHelper member `tex_helper_` (the elevation-map RACER models) */
-template <class T>
-struct has_elevation_map<T, std::void_t<decltype(std::declval<T&>().tex_helper_.textures_[0].data)>> : std::true_type
-{
-};
-template <class T, class = void>
-struct has_mean_unc_networks : std::false_type
-{
-};
-/** dynamics with the mean and uncertainty LSTMs of RacerDubinsElevationLSTMUncertainty next to the steering one */
-template <class T>
-struct has_mean_unc_networks<T, std::void_t<decltype(std::declval<T&>().mean_lstm_d_), decltype(std::declval<T&>().unc_lstm_d_)>>
-  : std::true_type
-{
-};
-template <class T, class = void>
-struct has_normals_map : std::false_type
-{
-};
-/** dynamics with a second, four-channel map `normals_tex_helper_` (the suspension RACER models) */
-template <class T>
-struct has_normals_map<T, std::void_t<decltype(std::declval<T&>().normals_tex_helper_.textures_[0].data)>> : std::true_type
-{
-};
-template <class T, class = void>
-struct has_costmap : std::false_type
-{
-};
-template <class T>
-struct has_costmap<T, std::void_t<decltype(std::declval<T&>().costmap_d_)>> : std::true_type
-{
-};
-/** channels of a has_costmap cost's map: `static constexpr int COSTMAP_CHANNELS = 4;` in the class (ARRobustCost: interleaved
- *  float[height][width][4] texels); absent: 1, a plain float[height][width] (ARStandardCost) */
-template <class T, class = void>
-struct costmap_channels : std::integral_constant<int, 1>
-{
-};
-template <class T>
-struct costmap_channels<T, std::void_t<decltype(T::COSTMAP_CHANNELS)>> : std::integral_constant<int, T::COSTMAP_CHANNELS>
-{
-};
-template <class T, class = void>
-struct has_cost_texture : std::false_type
-{
-};
-/** a cost with a TwoDTextureHelper member `tex_helper_` (QuadrotorMapCost: the track map); ARStandardCost's costmap_d_ / r_c1
- *  form is has_costmap, and a class is one or the other (static_assert in ModelT) */
-template <class T>
-struct has_cost_texture<T, std::void_t<decltype(std::declval<T&>().tex_helper_.textures_[0].data)>> : std::true_type
-{
-};
-
 /**
  * DYN_FAST_T / FAST_SHAPES: an optional second Dynamics type implementing the same model for particular block shapes
  * (e.g. the MFMA forward of the NN model for shape (16, 4)); it is constructed from the primary object at launch, so
@@ -658,17 +276,8 @@ struct ModelT : ModelBase
         const bool in_loop = SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
         auto kfn = in_loop ? kernels::rolloutRMPPIPipelineKernel<PD_T, COST_T, DeviceDDP<DYN_T>, SAMPLING_T, SAMPLING_T::IN_LOOP_DRAW>
                            : kernels::rolloutRMPPIPipelineKernel<PD_T, COST_T, DeviceDDP<DYN_T>, SAMPLING_T, false>;
-        if (smem > 48 * 1024)
-          (void)ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
-        hipLaunchKernelGGL(kfn, dim3((a.base.num_rollouts + 63) / 64), dim3(64 * kernels::rmppiPipelineWaves<PD_T>(), 1, 1), smem,
-                           stream, pd, cost, fb, smp, a, r);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-        {
-          err = std::string("rolloutRMPPIPipelineKernel launch: ") + hipGetErrorString(e);
-          return MPPI_ERR_HIP;
-        }
-        return MPPI_OK;
+        return launchChecked("rolloutRMPPIPipelineKernel", kfn, dim3((a.base.num_rollouts + 63) / 64),
+                             dim3(64 * kernels::rmppiPipelineWaves<PD_T>(), 1, 1), smem, stream, err, pd, cost, fb, smp, a, r);
       });
     }
     err = "model has no role-pipelined Robust MPPI kernel";
@@ -699,18 +308,9 @@ struct ModelT : ModelBase
             constexpr int REP = kernels::replicated_lanes<PD_T>::value;
             const size_t smem = kernels::initEvalPipelineSharedBytes(pd, cost, a.num_timesteps, ring);
             auto kfn = kernels::initEvalPipelineKernel<PD_T, COST_T, SAMPLING_T>;
-            if (smem > 48 * 1024)
-              (void)ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
             constexpr int WAVES = REP + kernels::INIT_EVAL_PIPE_SAMPLERS + kernels::INIT_EVAL_PIPE_COSTS;
-            hipLaunchKernelGGL(kfn, dim3((a.num_eval_rollouts + BX - 1) / BX), dim3(64 * WAVES, 1, 1), smem, stream, pd, cost, smp, a,
-                               ring);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess)
-            {
-              err = std::string("initEvalPipelineKernel launch: ") + hipGetErrorString(e);
-              return MPPI_ERR_HIP;
-            }
-            return MPPI_OK;
+            return launchChecked("initEvalPipelineKernel", kfn, dim3((a.num_eval_rollouts + BX - 1) / BX), dim3(64 * WAVES, 1, 1), smem,
+                                 stream, err, pd, cost, smp, a, ring);
           });
           if (launched || st != MPPI_OK)
             return st;
@@ -722,17 +322,8 @@ struct ModelT : ModelBase
         constexpr int REP = kernels::replicated_lanes<RM_DYN_T>::value;
         const size_t smem = kernels::initEvalSharedBytes<RM_DYN_T, COST_T, SAMPLING_T>(rm_dyn, cost, BX);
         auto kfn = kernels::initEvalKernel<RM_DYN_T, COST_T, SAMPLING_T, BX>;
-        if (smem > 48 * 1024)
-          (void)ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
-        hipLaunchKernelGGL(kfn, dim3((a.num_eval_rollouts + BX - 1) / BX), dim3(BX * REP, 1, 1), smem, stream, rm_dyn, cost,
-                           smp, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-        {
-          err = std::string("initEvalKernel launch: ") + hipGetErrorString(e);
-          return MPPI_ERR_HIP;
-        }
-        return MPPI_OK;
+        return launchChecked("initEvalKernel", kfn, dim3((a.num_eval_rollouts + BX - 1) / BX), dim3(BX * REP, 1, 1), smem, stream,
+                             err, rm_dyn, cost, smp, a);
       });
     }
     return ModelBase::launchInitEval(pipeline, a, s, stream, err);
@@ -747,24 +338,12 @@ struct ModelT : ModelBase
         constexpr int REP = kernels::replicated_lanes<RM_DYN_T>::value;
         const size_t smem = kernels::rmppiSharedBytes(rm_dyn, cost, fb, smp, BX);
         if (smem > MAX_LDS_BYTES)
-        {
-          err = "RMPPI rollout kernel needs " + std::to_string(smem) + " B of LDS per block; gfx950 has 163840";
-          return MPPI_ERR_LDS_OVERFLOW;
-        }
+          return ldsOverflow("RMPPI rollout kernel", smem, err);
         const bool in_loop = SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
         auto kfn = in_loop ? kernels::rolloutRMPPIKernel<RM_DYN_T, COST_T, DeviceDDP<DYN_T>, SAMPLING_T, BX, SAMPLING_T::IN_LOOP_DRAW>
                            : kernels::rolloutRMPPIKernel<RM_DYN_T, COST_T, DeviceDDP<DYN_T>, SAMPLING_T, BX, false>;
-        if (smem > 48 * 1024)
-          (void)ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
-        hipLaunchKernelGGL(kfn, dim3((a.base.num_rollouts + BX - 1) / BX), dim3(BX * REP, 1, 2), smem, stream, rm_dyn, cost, fb,
-                           smp, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-        {
-          err = std::string("rolloutRMPPIKernel launch: ") + hipGetErrorString(e);
-          return MPPI_ERR_HIP;
-        }
-        return MPPI_OK;
+        return launchChecked("rolloutRMPPIKernel", kfn, dim3((a.base.num_rollouts + BX - 1) / BX), dim3(BX * REP, 1, 2), smem, stream,
+                             err, rm_dyn, cost, fb, smp, a);
       });
     }
     err = "model is not registered for Robust MPPI";
@@ -880,17 +459,9 @@ struct ModelT : ModelBase
           kfn = in_loop ? kernels::rolloutPipelineRepKernel<FAST, COST_T, SAMPLING_T, SAMPLING_T::IN_LOOP_DRAW, true>
                         : kernels::rolloutPipelineRepKernel<FAST, COST_T, SAMPLING_T, false, true>;
       }
-      if (smem > 48 * 1024)
-        (void)ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
       constexpr int WAVES = REP + kernels::PIPE_REP_SAMPLERS + kernels::PIPE_REP_COSTS;  // dynamics + helper waves
-      hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * WAVES, 1, 1), smem, stream, fast, cost, smp, args, ring);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess)
-      {
-        err = std::string("rolloutPipelineRepKernel launch: ") + hipGetErrorString(e);
-        return MPPI_ERR_HIP;
-      }
-      return MPPI_OK;
+      return launchChecked("rolloutPipelineRepKernel", kfn, dim3(grid), dim3(64 * WAVES, 1, 1), smem, stream, err, fast, cost, smp,
+                           args, ring);
     }
     err = "model has no replicated-lane dynamics";
     return MPPI_ERR_LAUNCH_SHAPE;
@@ -907,10 +478,7 @@ struct ModelT : ModelBase
     {
       const size_t smem = kernels::pipelineSharedBytes(dyn, cost, smp, Z, FOLD);
       if (smem > MAX_LDS_BYTES)
-      {
-        err = "pipeline rollout kernel needs " + std::to_string(smem) + " B of LDS per block; gfx950 has 163840";
-        return MPPI_ERR_LDS_OVERFLOW;
-      }
+        return ldsOverflow("pipeline rollout kernel", smem, err);
       const bool in_loop = SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
       auto kfn = in_loop ? kernels::rolloutPipelineKernel<DYN_T, COST_T, SAMPLING_T, Z, SAMPLING_T::IN_LOOP_DRAW, FOLD>
                          : kernels::rolloutPipelineKernel<DYN_T, COST_T, SAMPLING_T, Z, false, FOLD>;
@@ -936,19 +504,10 @@ struct ModelT : ModelBase
         err = "prev_records_d: the streamed merge exists for one-system Gaussian pipeline launches only";
         return MPPI_ERR_STATE;
       }
-      if (smem > 48 * 1024)
-        (void)ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
       constexpr int RPB = FOLD ? 64 / Z : 64;  // rollouts per block
       const int grid = (args.num_rollouts + RPB - 1) / RPB;
-      hipLaunchKernelGGL(kfn, dim3(grid), dim3(kernels::pipelineBlockX(Z, FOLD), 1, FOLD ? 1 : Z), smem, stream, dyn, cost,
-                         smp, args);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess)
-      {
-        err = std::string("rolloutPipelineKernel launch: ") + hipGetErrorString(e);
-        return MPPI_ERR_HIP;
-      }
-      return MPPI_OK;
+      return launchChecked("rolloutPipelineKernel", kfn, dim3(grid), dim3(kernels::pipelineBlockX(Z, FOLD), 1, FOLD ? 1 : Z), smem,
+                           stream, err, dyn, cost, smp, args);
     }
     err = "model is not registered for the pipeline variant";
     return MPPI_ERR_LAUNCH_SHAPE;
@@ -971,22 +530,7 @@ struct ModelT : ModelBase
   bool normals_transform_set = false;
   HipBuffer<float> extra_net_d[4];  ///< mean LSTM, mean MLP, uncertainty LSTM, uncertainty MLP
 
-  /** frees the old blob, then uploads the new one */
-  static mppi_status upload(HipBuffer<float>& dst, const float* src, size_t count, hipStream_t stream, std::string& err)
-  {
-    hipError_t e = dst.alloc(count);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(dst, src, count * sizeof(float), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess)
-      e = hipStreamSynchronize(stream);
-    if (e != hipSuccess)
-    {
-      err = std::string("blob upload: ") + hipGetErrorString(e);
-      return MPPI_ERR_HIP;
-    }
-    return MPPI_OK;
-  }
-
+  /** the checks, uploads and bindings are model_blobs.hpp's; here: which blob names a model has, and where each one goes */
   mppi_status setBlob(const std::string& name, const float* data, size_t count, const int* dims, int ndims,
                       hipStream_t stream, std::string& err) override
   {
@@ -994,13 +538,9 @@ struct ModelT : ModelBase
     {
       if (name == "dynamics_weights")
       {
-        if ((int)count != dyn.helper_.NUM_PARAMS)
-        {
-          err = "dynamics_weights: expected " + std::to_string(dyn.helper_.NUM_PARAMS) + " floats, got " +
-                std::to_string(count);
+        if (!expectCount(name, count, dyn.helper_.NUM_PARAMS, err))
           return MPPI_ERR_INVALID_ARG;
-        }
-        mppi_status st = upload(weights_d, data, count, stream, err);
+        const mppi_status st = uploadBlob(weights_d, data, count, stream, err);
         dyn.helper_.theta_d_ = weights_d;
         return st;
       }
@@ -1011,9 +551,7 @@ struct ModelT : ModelBase
        * {hidden size, output-network layer sizes ...} as floats, given before the weights */
       if (name == "lstm_structure")
       {
-        std::vector<int> desc(count);
-        for (size_t i = 0; i < count; i++)
-          desc[i] = (int)data[i];
+        const std::vector<int> desc(data, data + count);
         if (!dyn.setLSTMStructure(desc.data(), (int)count))
         {
           err = "lstm_structure: expected {H, H + inputs, ..., outputs} with at least one output-network layer";
@@ -1028,76 +566,41 @@ struct ModelT : ModelBase
     {
       if (name == "lstm_weights")
       {
-        if ((int)count != dyn.lstm_.getNumParams())
-        {
-          err = "lstm_weights: expected " + std::to_string(dyn.lstm_.getNumParams()) + " floats, got " +
-                std::to_string(count);
+        if (!expectCount(name, count, dyn.lstm_.getNumParams(), err))
           return MPPI_ERR_INVALID_ARG;
-        }
-        mppi_status st = upload(weights_d, data, count, stream, err);
+        const mppi_status st = uploadBlob(weights_d, data, count, stream, err);
         dyn.lstm_.weights_d_ = weights_d;
         return st;
       }
       if (name == "lstm_output_weights")
       {
-        if ((int)count != dyn.lstm_.output_nn_.NUM_PARAMS)
-        {
-          err = "lstm_output_weights: expected " + std::to_string(dyn.lstm_.output_nn_.NUM_PARAMS) + " floats, got " +
-                std::to_string(count);
+        if (!expectCount(name, count, dyn.lstm_.output_nn_.NUM_PARAMS, err))
           return MPPI_ERR_INVALID_ARG;
-        }
-        mppi_status st = upload(weights2_d, data, count, stream, err);
+        const mppi_status st = uploadBlob(weights2_d, data, count, stream, err);
         dyn.lstm_.output_nn_.theta_d_ = weights2_d;
         return st;
       }
     }
     if constexpr (has_elevation_map<DYN_T>::value)
     {
-      /* TwoDTextureHelper::updateTexture + enableTexture (texture_helper.cu:135-190): {height, width} heights, row-major */
+      /* {height, width} heights, row-major */
       if (name == "elevation_map")
       {
-        if (ndims != 2 || dims[0] <= 0 || dims[1] <= 0 || (size_t)dims[0] * dims[1] != count)
-        {
-          err = "elevation_map: dims must be {height, width} with height*width == count";
+        if (!checkMapDims(name, dims, ndims, count, 1, err))
           return MPPI_ERR_INVALID_ARG;
-        }
-        mppi_status st = upload(elevation_d, data, count, stream, err);
-        auto& tex = dyn.tex_helper_.textures_[0];
-        tex.data = elevation_d;
-        tex.height = dims[0];
-        tex.width = dims[1];
-        tex.use = (st == MPPI_OK);
+        const mppi_status st = uploadBlob(elevation_d, data, count, stream, err);
+        bindMap(dyn.tex_helper_.textures_[0], elevation_d, dims, st);
         return st;
       }
-      /* updateOrigin / updateRotation / updateResolution (texture_helper.cu:192-268): origin[3], rotations[9] row-major,
-       * resolution[3] */
       if (name == "elevation_map_transform")
       {
-        if (count != 15)
-        {
-          err = "elevation_map_transform: expected 15 floats (origin[3], rotations[9], resolution[3])";
+        if (!expectFrameCount(name, count, err))
           return MPPI_ERR_INVALID_ARG;
-        }
-        auto& tex = dyn.tex_helper_.textures_[0];
-        for (int i = 0; i < 3; i++)
-          tex.origin[i] = data[i];
-        for (int i = 0; i < 9; i++)
-          tex.rotations[i] = data[3 + i];
-        for (int i = 0; i < 3; i++)
-          tex.resolution[i] = data[12 + i];
+        setMapFrame(dyn.tex_helper_.textures_[0], data);
         if constexpr (has_normals_map<DYN_T>::value)
         {  // the normals map shares the frame unless it was given its own
           if (!normals_transform_set)
-          {
-            auto& ntex = dyn.normals_tex_helper_.textures_[0];
-            for (int i = 0; i < 3; i++)
-            {
-              ntex.origin[i] = tex.origin[i];
-              ntex.resolution[i] = tex.resolution[i];
-            }
-            for (int i = 0; i < 9; i++)
-              ntex.rotations[i] = tex.rotations[i];
-          }
+            setMapFrame(dyn.normals_tex_helper_.textures_[0], data);
         }
         return MPPI_OK;
       }
@@ -1112,9 +615,7 @@ struct ModelT : ModelBase
         /* another hidden size / output network than the reference's test shapes: {H, H + inputs, ..., outputs} as floats,
          * given before the weights (the reference sizes the networks from the file, lstm_helper.cu:13-62) */
         const int which = name[0] == 'm' ? 1 : 2;
-        std::vector<int> desc(count);
-        for (size_t i = 0; i < count; i++)
-          desc[i] = (int)data[i];
+        const std::vector<int> desc(data, data + count);
         if (!dyn.setNetworkStructure(which, desc.data(), (int)count))
         {
           err = name + ": expected {H, H + inputs, ..., outputs} with the model's input / output sizes (12 -> 2, 13 -> 5)";
@@ -1144,11 +645,8 @@ struct ModelT : ModelBase
       {
         if (name != nets[i].name)
           continue;
-        if (count != nets[i].count)
-        {
-          err = name + ": expected " + std::to_string(nets[i].count) + " floats, got " + std::to_string(count);
+        if (!expectCount(name, count, nets[i].count, err))
           return MPPI_ERR_INVALID_ARG;
-        }
         if (i >= 4)
         {  // initial hidden / cell state into the tail of the uploaded LSTM blob
           float* blob = extra_net_d[nets[i].slot];
@@ -1158,17 +656,9 @@ struct ModelT : ModelBase
             return MPPI_ERR_STATE;
           }
           const size_t params = (size_t)(i == 4 ? dyn.mean_lstm_.LSTM_NUM_PARAMS : dyn.unc_lstm_.LSTM_NUM_PARAMS);
-          hipError_t e = hipMemcpyAsync(blob + params, data, count * sizeof(float), hipMemcpyHostToDevice, stream);
-          if (e == hipSuccess)
-            e = hipStreamSynchronize(stream);
-          if (e != hipSuccess)
-          {
-            err = std::string("LSTM state upload: ") + hipGetErrorString(e);
-            return MPPI_ERR_HIP;
-          }
-          return MPPI_OK;
+          return uploadTail(blob, params, data, count, "LSTM state upload", stream, err);
         }
-        mppi_status st = upload(extra_net_d[nets[i].slot], data, count, stream, err);
+        const mppi_status st = uploadBlob(extra_net_d[nets[i].slot], data, count, stream, err);
         // only what was uploaded for the present shapes (a structure blob clears its network's pair)
         if (nets[i].slot == 0)
           dyn.mean_lstm_.weights_d_ = dyn.mean_lstm_d_ = extra_net_d[0];
@@ -1187,33 +677,17 @@ struct ModelT : ModelBase
        * set-up tests/dynamics/racer_dubins_elevation_suspension_test.cu:170-190): {height, width, 4} = nx, ny, nz, unused */
       if (name == "normals_map")
       {
-        if (ndims != 3 || dims[0] <= 0 || dims[1] <= 0 || dims[2] != 4 || (size_t)dims[0] * dims[1] * 4 != count)
-        {
-          err = "normals_map: dims must be {height, width, 4} with height*width*4 == count";
+        if (!checkMapDims(name, dims, ndims, count, 4, err))
           return MPPI_ERR_INVALID_ARG;
-        }
-        mppi_status st = upload(normals_d, data, count, stream, err);
-        auto& tex = dyn.normals_tex_helper_.textures_[0];
-        tex.data = normals_d;
-        tex.height = dims[0];
-        tex.width = dims[1];
-        tex.use = (st == MPPI_OK);
+        const mppi_status st = uploadBlob(normals_d, data, count, stream, err);
+        bindMap(dyn.normals_tex_helper_.textures_[0], normals_d, dims, st);
         return st;
       }
       if (name == "normals_map_transform")
       {
-        if (count != 15)
-        {
-          err = "normals_map_transform: expected 15 floats (origin[3], rotations[9], resolution[3])";
+        if (!expectFrameCount(name, count, err))
           return MPPI_ERR_INVALID_ARG;
-        }
-        auto& tex = dyn.normals_tex_helper_.textures_[0];
-        for (int i = 0; i < 3; i++)
-          tex.origin[i] = data[i];
-        for (int i = 0; i < 9; i++)
-          tex.rotations[i] = data[3 + i];
-        for (int i = 0; i < 3; i++)
-          tex.resolution[i] = data[12 + i];
+        setMapFrame(dyn.normals_tex_helper_.textures_[0], data);
         normals_transform_set = true;
         return MPPI_OK;
       }
@@ -1222,26 +696,16 @@ struct ModelT : ModelBase
     {
       if (name == "costmap")
       {
+        /* CH > 1: interleaved texels, one CH-float texel per map cell (ARRobustCost: boundary, track position, speed, heading) */
         constexpr int CH = costmap_channels<COST_T>::value;
-        if constexpr (CH == 1)
+        if (!checkMapDims(name, dims, ndims, count, CH, err))
         {
-          if (ndims != 2 || dims[0] <= 0 || dims[1] <= 0 || (size_t)dims[0] * dims[1] != count)
-          {
-            err = "costmap: dims must be {height, width} with height*width == count";
-            return MPPI_ERR_INVALID_ARG;
-          }
-        }
-        else
-        {
-          /* interleaved texels, one CH-float texel per map cell (ARRobustCost: boundary, track position, speed, heading) */
-          if (ndims != 3 || dims[0] <= 0 || dims[1] <= 0 || dims[2] != CH || (size_t)dims[0] * dims[1] * CH != count)
-          {
+          if constexpr (CH > 1)
             err = "costmap: this model's cost reads " + std::to_string(CH) + " channels: dims must be {height, width, " +
                   std::to_string(CH) + "} (interleaved texels) with height*width*" + std::to_string(CH) + " == count";
-            return MPPI_ERR_INVALID_ARG;
-          }
+          return MPPI_ERR_INVALID_ARG;
         }
-        mppi_status st = upload(costmap_d, data, count, stream, err);
+        const mppi_status st = uploadBlob(costmap_d, data, count, stream, err);
         cost.costmap_d_ = costmap_d;
         cost.height_ = dims[0];
         cost.width_ = dims[1];
@@ -1250,37 +714,20 @@ struct ModelT : ModelBase
     }
     if constexpr (has_cost_texture<COST_T>::value)
     {
-      /* the cost's TwoDTextureHelper: updateTexture + enableTexture, {height, width} values, row-major; the model runs without it */
+      /* the cost's TwoDTextureHelper: {height, width} values, row-major; the model runs without it */
       if (name == "costmap")
       {
-        if (ndims != 2 || dims[0] <= 0 || dims[1] <= 0 || (size_t)dims[0] * dims[1] != count)
-        {
-          err = "costmap: dims must be {height, width} with height*width == count";
+        if (!checkMapDims(name, dims, ndims, count, 1, err))
           return MPPI_ERR_INVALID_ARG;
-        }
-        mppi_status st = upload(costmap_d, data, count, stream, err);
-        auto& tex = cost.tex_helper_.textures_[0];
-        tex.data = costmap_d;
-        tex.height = dims[0];
-        tex.width = dims[1];
-        tex.use = (st == MPPI_OK);
+        const mppi_status st = uploadBlob(costmap_d, data, count, stream, err);
+        bindMap(cost.tex_helper_.textures_[0], costmap_d, dims, st);
         return st;
       }
-      /* updateOrigin / updateRotation / updateResolution: origin[3], rotations[9] row-major, resolution[3] */
       if (name == "costmap_transform")
       {
-        if (count != 15)
-        {
-          err = "costmap_transform: expected 15 floats (origin[3], rotations[9], resolution[3])";
+        if (!expectFrameCount(name, count, err))
           return MPPI_ERR_INVALID_ARG;
-        }
-        auto& tex = cost.tex_helper_.textures_[0];
-        for (int i = 0; i < 3; i++)
-          tex.origin[i] = data[i];
-        for (int i = 0; i < 9; i++)
-          tex.rotations[i] = data[3 + i];
-        for (int i = 0; i < 3; i++)
-          tex.resolution[i] = data[12 + i];
+        setMapFrame(cost.tex_helper_.textures_[0], data);
         return MPPI_OK;
       }
     }
@@ -1297,24 +744,18 @@ struct ModelT : ModelBase
         return MPPI_ERR_STATE;
       }
       const int H = dyn.lstm_.HIDDEN_DIM;
+      std::vector<float> state(2 * (size_t)H);  // [hidden | cell], the layout behind the blob's parameters
       for (int i = 0; i < H; i++)
+      {
         if (!std::isfinite(hidden[i]) || !std::isfinite(cell[i]))
         {  // det::tanh(NaN) = -1: a NaN recurrent state would be masked, not propagated (see mppi_set_model_blob)
           err = "non-finite hidden / cell state";
           return MPPI_ERR_NAN;
         }
-      float* tail = weights_d + dyn.lstm_.LSTM_NUM_PARAMS;
-      hipError_t e = hipMemcpyAsync(tail, hidden, H * sizeof(float), hipMemcpyHostToDevice, stream);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(tail + H, cell, H * sizeof(float), hipMemcpyHostToDevice, stream);
-      if (e == hipSuccess)
-        e = hipStreamSynchronize(stream);  // the caller's buffers are pageable: they may go away after the call
-      if (e != hipSuccess)
-      {
-        err = std::string("LSTM initial state upload: ") + hipGetErrorString(e);
-        return MPPI_ERR_HIP;
+        state[i] = hidden[i];
+        state[H + i] = cell[i];
       }
-      return MPPI_OK;
+      return uploadTail(weights_d, dyn.lstm_.LSTM_NUM_PARAMS, state.data(), state.size(), "LSTM initial state upload", stream, err);
     }
     return ModelBase::setLSTMInitialState(hidden, cell, stream, err);
   }
@@ -1529,17 +970,8 @@ struct ModelT : ModelBase
       err = "noise dump kernel: the rows of 64 rollouts do not fit the LDS at this horizon";
       return MPPI_ERR_LDS_OVERFLOW;
     }
-    auto kfn = kernels::noiseDumpKernel<SAMPLING_T>;
-    if (smem > 48 * 1024)
-      (void)ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
-    hipLaunchKernelGGL(kfn, dim3((s.num_rollouts_local + 63) / 64), dim3(64, 1, 1), smem, stream, dump_smp, out_d);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-      err = std::string("noiseDumpKernel launch: ") + hipGetErrorString(e);
-      return MPPI_ERR_HIP;
-    }
-    return MPPI_OK;
+    return launchChecked("noiseDumpKernel", kernels::noiseDumpKernel<SAMPLING_T>, dim3((s.num_rollouts_local + 63) / 64),
+                         dim3(64, 1, 1), smem, stream, err, dump_smp, out_d);
   }
 
   template <int X, int Y, int Z, class... Rest>
@@ -1639,24 +1071,13 @@ struct ModelT : ModelBase
     static_assert(REP == Y, "fast shape: BY must equal the plugin's REPLICATED_LANES");
     const size_t smem = kernels::rolloutSharedBytes(fast, cost, smp, X, 1, Z);
     if (smem > MAX_LDS_BYTES)
-    {
-      err = "rollout kernel needs " + std::to_string(smem) + " B of LDS per block; gfx950 has 163840";
-      return MPPI_ERR_LDS_OVERFLOW;
-    }
+      return ldsOverflow("rollout kernel", smem, err);
     const bool in_loop = SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
     auto kfn = in_loop ? kernels::rolloutKernel<FAST, COST_T, SAMPLING_T, X, 1, Z, SAMPLING_T::IN_LOOP_DRAW>
                        : kernels::rolloutKernel<FAST, COST_T, SAMPLING_T, X, 1, Z, false>;
-    if (smem > 48 * 1024)
-      (void)ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
     const int grid = (args.num_rollouts + X - 1) / X;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(X * REP, 1, Z), smem, stream, fast, cost, smp, args);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-      err = std::string("rolloutKernel (fast variant) launch: ") + hipGetErrorString(e);
-      return MPPI_ERR_HIP;
-    }
-    return MPPI_OK;
+    return launchChecked("rolloutKernel (fast variant)", kfn, dim3(grid), dim3(X * REP, 1, Z), smem, stream, err, fast, cost, smp,
+                         args);
   }
   template <int X, int Y, int Z, class... Rest>
   mppi_status dispatchFast(Shapes<Shape<X, Y, Z>, Rest...>, int bx, int by, int bz, const kernels::RolloutArgs& args,
@@ -1680,32 +1101,13 @@ struct ModelT : ModelBase
   {
     const size_t smem = kernels::rolloutSharedBytes(dyn, cost, smp, X, Y, Z);
     if (smem > MAX_LDS_BYTES)
-    {
-      err = "rollout kernel needs " + std::to_string(smem) + " B of LDS per block; gfx950 has 163840";
-      return MPPI_ERR_LDS_OVERFLOW;
-    }
+      return ldsOverflow("rollout kernel", smem, err);
     // in-loop Philox draw needs one lane per rollout; otherwise the rows are pre-filled by initializeDistributions
     const bool in_loop = (Y == 1) && SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
     auto kfn = in_loop ? kernels::rolloutKernel<DYN_T, COST_T, SAMPLING_T, X, Y, Z, (Y == 1) && SAMPLING_T::IN_LOOP_DRAW>
                        : kernels::rolloutKernel<DYN_T, COST_T, SAMPLING_T, X, Y, Z, false>;
-    if (smem > 48 * 1024)
-    {
-      hipError_t e = ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
-      if (e != hipSuccess)
-      {
-        err = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e);
-        return MPPI_ERR_HIP;
-      }
-    }
     const int grid = (args.num_rollouts + X - 1) / X;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(X, Y, Z), smem, stream, dyn, cost, smp, args);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-      err = std::string("rolloutKernel launch: ") + hipGetErrorString(e);
-      return MPPI_ERR_HIP;
-    }
-    return MPPI_OK;
+    return launchChecked("rolloutKernel", kfn, dim3(grid), dim3(X, Y, Z), smem, stream, err, dyn, cost, smp, args);
   }
 
   template <int X, int Y, int Z, class... Rest>
@@ -1782,16 +1184,7 @@ struct ModelT : ModelBase
         if (smem_w <= MAX_LDS_BYTES)
         {
           auto kw = a.scratch_d ? kernels::finalizeRepKernel<WAVE_T, true> : kernels::finalizeRepKernel<WAVE_T, false>;
-          if (smem_w > 48 * 1024)
-            (void)ensureDynamicLds(reinterpret_cast<const void*>(kw), smem_w);
-          hipLaunchKernelGGL(kw, dim3(D), dim3(64, 1, 1), smem_w, stream, wave_form, a);
-          hipError_t e = hipGetLastError();
-          if (e != hipSuccess)
-          {
-            err = std::string("finalizeRepKernel (wave form) launch: ") + hipGetErrorString(e);
-            return MPPI_ERR_HIP;
-          }
-          return MPPI_OK;
+          return launchChecked("finalizeRepKernel (wave form)", kw, dim3(D), dim3(64, 1, 1), smem_w, stream, err, wave_form, a);
         }
       }
     }
@@ -1805,16 +1198,7 @@ struct ModelT : ModelBase
       if (usable)
       {
         auto krep = a.scratch_d ? kernels::finalizeRepKernel<DYN_FAST_T, true> : kernels::finalizeRepKernel<DYN_FAST_T, false>;
-        if (smem_rep > 48 * 1024)
-          (void)ensureDynamicLds(reinterpret_cast<const void*>(krep), smem_rep);
-        hipLaunchKernelGGL(krep, dim3(D), dim3(64, 1, 1), smem_rep, stream, fast, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-        {
-          err = std::string("finalizeRepKernel launch: ") + hipGetErrorString(e);
-          return MPPI_ERR_HIP;
-        }
-        return MPPI_OK;
+        return launchChecked("finalizeRepKernel", krep, dim3(D), dim3(64, 1, 1), smem_rep, stream, err, fast, a);
       }
     }
     const size_t smem = kernels::finalizeSharedBytes(dyn, a.num_timesteps, FIN_BY, a.scratch_d != nullptr);
@@ -1824,16 +1208,7 @@ struct ModelT : ModelBase
       return MPPI_ERR_LDS_OVERFLOW;
     }
     auto kfn = a.scratch_d ? kernels::finalizeKernel<DYN_T, FIN_BY, true> : kernels::finalizeKernel<DYN_T, FIN_BY, false>;
-    if (smem > 48 * 1024)
-      (void)ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
-    hipLaunchKernelGGL(kfn, dim3(D), dim3(kernels::finalizeBlockX(FIN_BY), FIN_BY, 1), smem, stream, dyn, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-      err = std::string("finalizeKernel launch: ") + hipGetErrorString(e);
-      return MPPI_ERR_HIP;
-    }
-    return MPPI_OK;
+    return launchChecked("finalizeKernel", kfn, dim3(D), dim3(kernels::finalizeBlockX(FIN_BY), FIN_BY, 1), smem, stream, err, dyn, a);
   }
 
   /** plain one-wave finalize form only (FIN_BY == 1, no replicated-lane / wave form): what the one-lane pipeline models have */
@@ -1857,17 +1232,8 @@ struct ModelT : ModelBase
         return MPPI_ERR_LAUNCH_SHAPE;
       }
       const size_t smem = kernels::mergeControlSharedBytes(dyn, a.num_timesteps);
-      auto kfn = kernels::mergeControlKernel<DYN_T>;
-      if (smem > 48 * 1024)
-        (void)ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
-      hipLaunchKernelGGL(kfn, dim3(1), dim3(64 * kernels::MERGE_CONTROL_WAVES, 1, 1), smem, stream, dyn, a, m);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess)
-      {
-        err = std::string("mergeControlKernel launch: ") + hipGetErrorString(e);
-        return MPPI_ERR_HIP;
-      }
-      return MPPI_OK;
+      return launchChecked("mergeControlKernel", kernels::mergeControlKernel<DYN_T>, dim3(1),
+                           dim3(64 * kernels::MERGE_CONTROL_WAVES, 1, 1), smem, stream, err, dyn, a, m);
     }
     err = "model has no merging control phase";
     return MPPI_ERR_LAUNCH_SHAPE;
@@ -1882,15 +1248,8 @@ struct ModelT : ModelBase
     const size_t smem = calcClassSharedMemSize(&dyn, 1) +
                         sizeof(float) * (3 * math::nearest_multiple_4(Sd) + math::nearest_multiple_4(Cd) +
                                          math::nearest_multiple_4(Od));
-    hipLaunchKernelGGL((modelStepKernel<DYN_T, FIN_BY>), dim3(1), dim3(1, FIN_BY, 1), smem, stream, dyn, x_d, u_d, dt,
-                       enforce);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-      err = std::string("modelStepKernel launch: ") + hipGetErrorString(e);
-      return MPPI_ERR_HIP;
-    }
-    return MPPI_OK;
+    return launchChecked("modelStepKernel", modelStepKernel<DYN_T, FIN_BY>, dim3(1), dim3(1, FIN_BY, 1), smem, stream, err, dyn, x_d,
+                         u_d, dt, enforce);
   }
 
   bool hasComputeGrad() const override
@@ -1915,21 +1274,10 @@ struct ModelT : ModelBase
         return MPPI_ERR_INVALID_ARG;
       }
       const size_t smem = kernels::linearizeSharedBytes(dyn);
-      auto kfn = kernels::linearizeKernel<DYN_T>;
-      hipError_t e = ensureDynamicLds(reinterpret_cast<const void*>(kfn), smem);
-      if (e == hipSuccess)
-      {
-        constexpr int P = kernels::linearizeBlockPoints<DYN_T>();
-        hipLaunchKernelGGL(kfn, dim3((a.n + P - 1) / P), dim3(64 * kernels::linearizeBlockWaves<DYN_T>(), 1, 1), smem, stream, dyn,
-                           a, kernels::linearizeModelSharedBytes(dyn));
-        e = hipGetLastError();
-      }
-      if (e != hipSuccess)
-      {
-        err = std::string("linearizeKernel launch: ") + hipGetErrorString(e);
-        return MPPI_ERR_HIP;
-      }
-      return MPPI_OK;
+      constexpr int P = kernels::linearizeBlockPoints<DYN_T>();
+      return launchChecked("linearizeKernel", kernels::linearizeKernel<DYN_T>, dim3((a.n + P - 1) / P),
+                           dim3(64 * kernels::linearizeBlockWaves<DYN_T>(), 1, 1), smem, stream, err, dyn, a,
+                           kernels::linearizeModelSharedBytes(dyn));
     }
     return ModelBase::launchLinearize(a, stream, err);
   }
