@@ -5,7 +5,8 @@
  * include/mppi_amd/engine/.
  *
  * Round 6 split the single 4 300-line engine.hip by concern (same C ABI, same tests):
- *   engine_core.hip         version / model table / lifecycle (mppi_create, mppi_destroy) / parameters / blobs, .npz, rocRAND
+ *   engine_core.hip         version / model table / mppi_destroy / parameters / blobs, .npz, rocRAND
+ *   engine_create.hip       mppi_create: the checks, the launch plan (launch_plan.hpp: which rollout kernel a handle runs), buffers
  *   engine_iteration.hip    one optimisation iteration: rollout launch, merges (fused, streamed, reference order, Tsallis),
  *                           the exchange inside an iteration, the post-processing pass
  *   engine_controllers.hip  mppi_compute_control for the Vanilla / Colored, Tube and Robust controllers, hand-over (inbox,
