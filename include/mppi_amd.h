@@ -33,7 +33,8 @@ extern "C" {
 #endif
 
 #define MPPI_AMD_VERSION_MAJOR 0
-#define MPPI_AMD_VERSION_MINOR 3 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory */
+#define MPPI_AMD_VERSION_MINOR 4 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory; 4: mppi_set_feedback_params,
+                                    mppi_compute_feedback, mppi_compute_feedback_at */
 
 typedef struct mppi_handle_s* mppi_handle;
 
@@ -453,6 +454,33 @@ mppi_status mppi_linearize(mppi_handle h, const float* x, const float* u, int n,
  */
 mppi_status mppi_linearize_trajectory(mppi_handle h, int system, float* A_out, float* B_out);
 
+/* ---------------------------------------------------------------- DDP tracking gains ----------------------------- */
+/* The time-varying gains K_t of the reference's DDPFeedback::computeFeedback (feedback_controllers/DDP/ddp.cu:91-120), what its
+ * Controller::computeFeedback and RobustMPPI::computeNominalFeedbackGains end in: with DDPParams::num_iterations = 1 (its default)
+ * exactly one backward pass of ddp/ddp.h:77-127 over Phi_t = I + A_t dt, Bd_t = B_t dt with the tracking cost's Q, R (times dt) and
+ * the terminal Q_f.  Computed on the device: linearizeKernel, then ddpBackwardKernel reading its A, B where they lie
+ * (mppi_amd/engine/feedback_kernel.hpp; the arithmetic: mppi_amd/feedback_controllers/ddp_backward.hpp), on the handle's stream;
+ * A and B never travel to the host.  gains[T][S][C], entry [t][i][j] = K_t(j, i) — the layout mppi_set_feedback_gains takes and
+ * DDPFeedbackState::fb_gain_traj_ has; row T - 1 is zero, as in the reference.  dt is the handle's. */
+/** Q[S][S], R[C][C], Qf[S][S] of DDPParams, row-major; a null matrix is the identity (the DDPParams default, also what a handle
+ *  uses that never called this).  Qf enters symmetrised, 0.5 (Qf + Qf^T).  num_iterations != 1: MPPI_ERR_UNSUPPORTED (the forward
+ *  pass and line search of ddp.h:129-162 are not built), nothing changes. */
+mppi_status mppi_set_feedback_params(mppi_handle h, const float* Q, const float* R, const float* Qf, int num_iterations);
+/**
+ * The gains along the (state, control) sequence mppi_linearize_trajectory(h, system, ...) would linearise, with its refusals
+ * (MPPI_ERR_STATE before the first mppi_compute_control, MPPI_ERR_UNSUPPORTED without computeGrad, MPPI_ERR_INVALID_ARG for the
+ * system).  gains_out[T][S][C] may be NULL.  On a Robust handle with system == 1 (the nominal sequences) a successful result is
+ * also installed as the handle's gains, device to device, as mppi_set_feedback_gains would with the accumulate flag last set
+ * there (default 0); before such a handle's first mppi_compute_control (which it cannot run without gains) the sequences are the
+ * nominal ones mppi_update_importance_sampling_control left, where the reference computes its first gains.  A pivot of quu that is not positive and finite: MPPI_ERR_NAN, the step in mppi_last_error; gains_out is
+ * not written, nothing is installed, gains set earlier stay in force.
+ */
+mppi_status mppi_compute_feedback(mppi_handle h, int system, float* gains_out);
+/** the same at the caller's points x[T][S], u[T][C] (host arrays) — for instance the reference's own linearisation points, its
+ *  explicit-Euler roll from the initial state with clamped controls (ddp.h:61-71).  Never installs anything.
+ *  MPPI_ERR_INVALID_ARG for a null x or u. */
+mppi_status mppi_compute_feedback_at(mppi_handle h, const float* x, const float* u, float* gains_out);
+
 /* ---------------------------------------------------------------- Robust MPPI (MPPI_CONTROLLER_ROBUST) ----------- */
 /* Systems of a Robust-MPPI handle: 0 = nominal, 1 = real (robust_mppi_controller.cu:637-640); x0 of
  * mppi_compute_control is the REAL state, mppi_get_control_seq the real system's control (getControlSeq),
@@ -465,7 +493,7 @@ mppi_status mppi_set_rmppi_params(mppi_handle h, float value_function_threshold,
                                   int samples_per_candidate);
 /**
  * DDP tracking-controller gains, the reference's DDPFeedbackState::fb_gain_traj_ (feedback_controllers/DDP/ddp.cuh:18-60):
- * gains[T][S][C], entry [t][i][j] = K_t(j, i).  The producer (host DDP / iLQR, include/mppi/ddp/) is the caller's.
+ * gains[T][S][C], entry [t][i][j] = K_t(j, i).  The producer is the caller's, or mppi_compute_feedback above.
  * accumulate_all_states == 0 reproduces DeviceDDPImpl::k (ddp.cu:11-45) including its behaviour for an even
  * CONTROL_DIM (only the last state's gain row takes effect); != 0 sums over all states.
  */
@@ -474,7 +502,7 @@ mppi_status mppi_set_feedback_gains(mppi_handle h, const float* gains, int accum
  * RobustMPPIController::updateImportanceSamplingControl(state, stride) (robust_mppi_controller.cu:548-568): candidate
  * nominal states by line search, init-eval kernel (core/rmppi_kernels.cu:231-356), best candidate by free energy,
  * control histories, slide of the nominal control, nominal state trajectory.  The DDP gain update that ends the
- * reference's function is the caller's (mppi_set_feedback_gains).
+ * reference's function is a call of the caller's: mppi_compute_feedback(h, 1, NULL), or mppi_set_feedback_gains.
  */
 mppi_status mppi_update_importance_sampling_control(mppi_handle h, const float* state, int stride);
 /** getNominalState, getBestIndex, nominal stride, getCandidateFreeEnergy [num_candidates]; any pointer may be NULL */

@@ -196,6 +196,28 @@ public:
     B.resize((size_t)num_timesteps_ * state_dim_ * control_dim_);
     check(mppi_linearize_trajectory(h_, system, A.data(), B.data()));
   }
+  /** DDPParams of the tracking controller (mppi_set_feedback_params): Q[S][S], R[C][C], Q_f[S][S] row-major, a null pointer is
+   *  the identity; num_iterations other than 1 throws (MPPI_ERR_UNSUPPORTED) */
+  void setFeedbackParams(const float* Q, const float* R, const float* Q_f, int num_iterations = 1)
+  {
+    check(mppi_set_feedback_params(h_, Q, R, Q_f, num_iterations));
+  }
+  /** the DDP tracking gains [T][S][C], [t][i][j] = K_t(j, i), along the result of the last computeControl, linearised and solved
+   *  on the device (mppi_compute_feedback; system 1: the nominal sequences of a Tube / Robust controller, which a Robust
+   *  controller also installs as its gains) */
+  std::vector<float> computeFeedback(int system = 0)
+  {
+    std::vector<float> g((size_t)num_timesteps_ * state_dim_ * control_dim_);
+    check(mppi_compute_feedback(h_, system, g.data()));
+    return g;
+  }
+  /** the same at the caller's points states[T][S], controls[T][C] (mppi_compute_feedback_at); installs nothing */
+  std::vector<float> computeFeedbackAt(const float* states, const float* controls)
+  {
+    std::vector<float> g((size_t)num_timesteps_ * state_dim_ * control_dim_);
+    check(mppi_compute_feedback_at(h_, states, controls, g.data()));
+    return g;
+  }
   std::vector<float> getTargetOutputSeq() const
   {
     std::vector<float> y((size_t)num_timesteps_ * output_dim_);

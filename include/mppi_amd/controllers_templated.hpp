@@ -32,6 +32,8 @@
 #include "mppi_amd.h"
 #include "mppi_amd/controllers.hpp"
 #include "mppi_amd/engine/model_registry.hpp"
+#include <functional>
+
 #include "mppi_amd/feedback_controllers/ddp_feedback.hpp"
 #include "mppi_amd/plugin/dynamics_host.hpp"
 #include "mppi_amd/sampling_distributions/colored_noise.hpp"
@@ -145,7 +147,10 @@ public:
   virtual ~ControllerBase()
   {
     if (h_)
+    {
+      bindFeedback(fb_controller_, nullptr, 0, std::function<void()>());
       mppi_destroy(h_);
+    }
   }
   ControllerBase(const ControllerBase&) = delete;
   ControllerBase& operator=(const ControllerBase&) = delete;
@@ -268,6 +273,21 @@ public:
       check(mppi_get_state_seq(h_, x.data()));
     return x;
   }
+  /** reference: controllers/controller.cuh computeFeedback(state) — fb_controller_->computeFeedback(state, target state
+   *  trajectory, control trajectory): the DDP gains along the last computeControl's result, computed on the device
+   *  (DDPFeedback::computeFeedback -> mppi_compute_feedback_at) and kept in the feedback object (getFeedbackGains()) */
+  void computeFeedback(const state_array& state)
+  {
+    ensureHandle();
+    syncPlugins();
+    fb_controller_->computeFeedback(state, getTargetStateSeq(), getControlSeq());
+  }
+  /** DDPParams for that computation (the reference's setFeedbackParams / fb_controller_->setParams) */
+  template <class FB_PARAMS_T>
+  void setFeedbackParams(const FB_PARAMS_T& fb_params)
+  {
+    fb_controller_->setParams(fb_params);
+  }
   output_trajectory getTargetOutputSeq() const
   {
     output_trajectory y = output_trajectory::Zero();
@@ -377,7 +397,25 @@ protected:
       throw Error(s, std::string("mppi_create: ") + mppi_last_error(nullptr));
     pushControllerParams();
     check(mppi_set_nominal_control(h_, init_control_traj_.data()));
+    bindFeedback(fb_controller_, h_, params_.num_timesteps_, std::function<void()>([this]() { syncPlugins(); }));
     afterCreate();
+  }
+  /** a feedback class that computes its gains through the engine (DDPFeedback::bindHandle) learns the handle; any other is left alone */
+  template <class F>
+  static auto bindFeedbackImpl(int, F* fb, mppi_handle h, int num_timesteps, const std::function<void()>& sync)
+      -> decltype(fb->bindHandle(h, num_timesteps, sync), void())
+  {
+    if (fb)
+      fb->bindHandle(h, num_timesteps, sync);
+  }
+  template <class F>
+  static void bindFeedbackImpl(long, F*, mppi_handle, int, const std::function<void()>&)
+  {
+  }
+  template <class F>
+  static void bindFeedback(F* fb, mppi_handle h, int num_timesteps, const std::function<void()>& sync)
+  {
+    bindFeedbackImpl(0, fb, h, num_timesteps, sync);
   }
   void pushControllerParams()
   {
@@ -585,6 +623,14 @@ public:
     if (this->h_)
       this->check(mppi_get_rmppi_state(this->h_, x.data(), nullptr, nullptr, nullptr));
     return x;
+  }
+  /** reference: robust_mppi_controller.cu computeNominalFeedbackGains(state) — the gains along the nominal state and control
+   *  trajectories, from the feedback object's computeFeedback; the next computeControl uploads them (syncPlugins) */
+  void computeNominalFeedbackGains(const state_array& state)
+  {
+    this->ensureHandle();
+    PARENT_CLASS::syncPlugins();
+    this->fb_controller_->computeFeedback(state, this->getTargetStateSeq(), getNominalControlSeq());
   }
   void setValueFunctionThreshold(float t)
   {

@@ -15,6 +15,7 @@
 #include "finalize_kernel.hpp"
 #include "rmppi_kernels.hpp"
 #include "linearize_kernel.hpp"
+#include "feedback_kernel.hpp"
 
 namespace mppi
 {
@@ -103,9 +104,10 @@ struct ModelBase
   {
     return false;
   }
-  /** DDP feedback gains [T][S][C] (ddp.cuh:18-60) -> device; accumulate_all_states: see ddp_feedback.hpp */
-  virtual mppi_status setFeedbackGains(const float* gains, int T, bool accumulate_all_states, hipStream_t stream,
-                                       std::string& err)
+  /** DDP feedback gains [T][S][C] (ddp.cuh:18-60) -> the model's device buffer; accumulate_all_states: see ddp_feedback.hpp;
+   *  gains_on_device: `gains` is device memory (the output of launchDdpBackward), copied on `stream` device to device */
+  virtual mppi_status setFeedbackGains(const float* gains, int T, bool accumulate_all_states, bool gains_on_device,
+                                       hipStream_t stream, std::string& err)
   {
     err = "model is not instantiated for Robust MPPI";
     return MPPI_ERR_UNSUPPORTED;
@@ -230,6 +232,13 @@ struct ModelBase
     err = "the model's Dynamics class declares no computeGrad";
     return MPPI_ERR_UNSUPPORTED;
   }
+  /** gains[T][S][C], status[2] <- the DDP backward pass over A[T][S][S], B[T][S][C] where launchLinearize left them: one launch of
+   *  kernels::ddpBackwardKernel<S, C> on `stream` (engine/feedback_kernel.hpp); default as above */
+  virtual mppi_status launchDdpBackward(const kernels::DdpBackwardArgs& a, hipStream_t stream, std::string& err)
+  {
+    err = "the model's Dynamics class declares no computeGrad";
+    return MPPI_ERR_UNSUPPORTED;
+  }
 };
 
 /** fingerprint of the structures a model translation unit and libmppi_amd.so exchange (mppi_register_model refuses a
@@ -240,15 +249,16 @@ struct ModelBase
  *  6: FinalizeArgs::phases / carry block of the split hand-over (round 5); 7: undeclaredBarrierFreePlugins; 8: the transposed
  *  record copy (RolloutArgs) and supportsMergeControl / launchMergeControl (both round 6); 9: LaunchRecord,
  *  listReplicatedLaneShapes / supportsRMPPIPipeline (the launch and model introspection of mppi_amd.h); 10: costmapChannels;
- *  11: hasComputeGrad / launchLinearize. */
-#define MPPI_ENGINE_ABI_VERSION 11
+ *  11: hasComputeGrad / launchLinearize; 12: launchDdpBackward, setFeedbackGains' gains_on_device. */
+#define MPPI_ENGINE_ABI_VERSION 12
 
 constexpr int engineAbiFingerprint()
 {
   return MPPI_ENGINE_ABI_VERSION * 1000003 +
          (int)(sizeof(ModelBase) + 131 * sizeof(kernels::RolloutArgs) + 131 * 131 * sizeof(kernels::FinalizeArgs) +
                7 * sizeof(kernels::RMPPIArgs) + 17 * sizeof(kernels::InitEvalArgs) + 31 * sizeof(SamplerLaunchState) +
-               37 * sizeof(kernels::MergeControlArgs) + 41 * sizeof(kernels::LinearizeArgs));
+               37 * sizeof(kernels::MergeControlArgs) + 41 * sizeof(kernels::LinearizeArgs) +
+               43 * sizeof(kernels::DdpBackwardArgs));
 }
 
 }  // namespace engine

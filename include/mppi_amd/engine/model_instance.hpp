@@ -128,7 +128,7 @@ struct ModelT : ModelBase
   {
     return RMPPI;
   }
-  mppi_status setFeedbackGains(const float* gains, int T, bool accumulate_all_states, hipStream_t stream,
+  mppi_status setFeedbackGains(const float* gains, int T, bool accumulate_all_states, bool gains_on_device, hipStream_t stream,
                                std::string& err) override
   {
     if constexpr (RMPPI)
@@ -142,7 +142,7 @@ struct ModelT : ModelBase
           e = gains_d.alloc(n);
       }
       if (e == hipSuccess)
-        e = hipMemcpyAsync(gains_d, gains, n * sizeof(float), hipMemcpyHostToDevice, stream);
+        e = hipMemcpyAsync(gains_d, gains, n * sizeof(float), gains_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream);
       if (e == hipSuccess)
         e = hipStreamSynchronize(stream);
       fb.fb_gain_traj_d_ = gains_d;  // null after a failed allocation, never a freed buffer
@@ -155,7 +155,7 @@ struct ModelT : ModelBase
       fb.accumulate_all_states_ = accumulate_all_states;
       return MPPI_OK;
     }
-    return ModelBase::setFeedbackGains(gains, T, accumulate_all_states, stream, err);
+    return ModelBase::setFeedbackGains(gains, T, accumulate_all_states, gains_on_device, stream, err);
   }
   /** Robust MPPI's two kernels run on the replicated-lane (FAST) form of a model when there is one — and when it is usable:
    *  the four-lane forms of the RACER models are compiled for the reference's network shapes, a network of another shape
@@ -1280,6 +1280,20 @@ struct ModelT : ModelBase
                            kernels::linearizeModelSharedBytes(dyn));
     }
     return ModelBase::launchLinearize(a, stream, err);
+  }
+  mppi_status launchDdpBackward(const kernels::DdpBackwardArgs& a, hipStream_t stream, std::string& err) override
+  {
+    if constexpr (mppi::has_compute_grad<DYN_T>::value)
+    {
+      if (a.T < 1 || !a.A_d || !a.B_d || !a.Q_d || !a.R_d || !a.Qf_d || !a.gains_d || !a.status_d)
+      {
+        err = "ddpBackwardKernel: T >= 1 steps and seven device pointers";
+        return MPPI_ERR_INVALID_ARG;
+      }
+      return launchChecked("ddpBackwardKernel", kernels::ddpBackwardKernel<DYN_T::STATE_DIM, DYN_T::CONTROL_DIM>, dim3(1),
+                           dim3(64, 1, 1), 0, stream, err, a);
+    }
+    return ModelBase::launchDdpBackward(a, stream, err);
   }
 };
 

@@ -143,6 +143,9 @@ SIGNATURES = {
     "mppi_has_compute_grad": (C.c_int, [H]),
     "mppi_linearize": (C.c_int, [H, _f32p, _f32p, C.c_int, _f32p, _f32p]),
     "mppi_linearize_trajectory": (C.c_int, [H, C.c_int, _f32p, _f32p]),
+    "mppi_set_feedback_params": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mppi_compute_feedback": (C.c_int, [H, C.c_int, C.c_void_p]),
+    "mppi_compute_feedback_at": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mppi_slide": (C.c_int, [H, C.c_int]),
     "mppi_get_costs": (C.c_int, [H, _f32p]),
     "mppi_get_stats": (C.c_int, [H, C.POINTER(MppiStats)]),

@@ -649,6 +649,40 @@ class MPPIController:
         self._check(self._lib.mppi_linearize_trajectory(self._h, system, A.reshape(-1), B.reshape(-1)))
         return A, B
 
+    def setFeedbackParams(self, Q=None, R=None, Q_f=None, num_iterations=1):
+        """DDPParams of the tracking controller (mppi_set_feedback_params): Q (S, S), R (C, C), Q_f (S, S); None is the identity,
+        the DDPParams default.  num_iterations other than 1 raises MPPIError(MPPI_ERR_UNSUPPORTED)."""
+        def mat(m, n, name):
+            if m is None:
+                return None, None
+            a = np.ascontiguousarray(m, np.float32)
+            if a.shape != (n, n):
+                raise MPPIError(MPPI_ERR_INVALID_ARG, "setFeedbackParams: %s is %s, expected (%d, %d)" % (name, a.shape, n, n))
+            return a, a.ctypes.data
+        q, qp = mat(Q, self.STATE_DIM, "Q")
+        r, rp = mat(R, self.CONTROL_DIM, "R")
+        f, fp = mat(Q_f, self.STATE_DIM, "Q_f")
+        self._check(self._lib.mppi_set_feedback_params(self._h, qp, rp, fp, int(num_iterations)))
+
+    def computeFeedback(self, system=0):
+        """the DDP tracking gains (T, S, C), [t][i][j] = K_t(j, i), along the result of the last computeControl, linearised and
+        solved on the device (mppi_compute_feedback): system 0 the sequences getTargetStateSeq / getControlSeq return, system 1
+        the nominal ones of a Tube / Robust controller — a Robust controller also installs that result as its gains"""
+        g = np.empty((self.num_timesteps, self.STATE_DIM, self.CONTROL_DIM), np.float32)
+        self._check(self._lib.mppi_compute_feedback(self._h, int(system), g.ctypes.data))
+        return g
+
+    def computeFeedbackAt(self, states, controls):
+        """the same at the caller's points, states (T, S) and controls (T, C) (mppi_compute_feedback_at); installs nothing"""
+        x = np.ascontiguousarray(states, np.float32).reshape(-1)
+        u = np.ascontiguousarray(controls, np.float32).reshape(-1)
+        if x.size != self.num_timesteps * self.STATE_DIM or u.size != self.num_timesteps * self.CONTROL_DIM:
+            raise MPPIError(MPPI_ERR_INVALID_ARG, "computeFeedbackAt: states (%d, %d) and controls (%d, %d) expected"
+                            % (self.num_timesteps, self.STATE_DIM, self.num_timesteps, self.CONTROL_DIM))
+        g = np.empty((self.num_timesteps, self.STATE_DIM, self.CONTROL_DIM), np.float32)
+        self._check(self._lib.mppi_compute_feedback_at(self._h, x.ctypes.data, u.ctypes.data, g.ctypes.data))
+        return g
+
     def getTargetOutputSeq(self):
         y = np.empty((self.num_timesteps, self.OUTPUT_DIM), np.float32)
         self._check(self._lib.mppi_get_output_seq(self._h, y))
@@ -803,7 +837,7 @@ class ColoredMPPIController(MPPIController):
 
 class RobustMPPIController(MPPIController):
     """reference: controllers/R-MPPI/robust_mppi_controller.cuh — RobustMPPIController.
-    Systems: 0 = nominal, 1 = real.  The DDP gain producer is the caller's (setFeedbackGains)."""
+    Systems: 0 = nominal, 1 = real.  The DDP gains come from the caller (setFeedbackGains) or from computeFeedback(system=1)."""
     KIND = MPPI_CONTROLLER_ROBUST
 
     def setRMPPIParams(self, value_function_threshold=1000.0, num_candidates=9, samples_per_candidate=32):

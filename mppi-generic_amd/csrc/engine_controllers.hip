@@ -836,9 +836,9 @@ int mppi_has_compute_grad(mppi_handle h)
   return h && h->model->hasComputeGrad() ? 1 : 0;
 }
 
-/** the Jacobians at the n points x_d[n][S], u_d[n][C] (device memory) into the caller's host arrays: one launch behind whatever
- *  the stream holds, two copies back, one synchronisation */
-static mppi_status linearizeOnDevice(mppi_handle h, const float* x_d, const float* u_d, int n, float* A_out, float* B_out)
+/** queues linearizeKernel for the n points x_d[n][S], u_d[n][C] (device memory) behind whatever the stream holds; A and B stay
+ *  in h->lin_out_d, where `a` says */
+static mppi_status linearizeLaunch(mppi_handle h, const float* x_d, const float* u_d, int n, kernels::LinearizeArgs& a)
 {
   const size_t nA = (size_t)n * h->S * h->S, nB = (size_t)n * h->S * h->C;
   if (h->lin_out_d.size() < nA + nB)
@@ -846,7 +846,7 @@ static mppi_status linearizeOnDevice(mppi_handle h, const float* x_d, const floa
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // an earlier launch may still write the old buffer
     HIP_TRY(h, h->lin_out_d.alloc(nA + nB));
   }
-  kernels::LinearizeArgs a{};
+  a = kernels::LinearizeArgs{};
   a.x_d = x_d;
   a.u_d = u_d;
   a.A_d = h->lin_out_d;
@@ -856,9 +856,32 @@ static mppi_status linearizeOnDevice(mppi_handle h, const float* x_d, const floa
   const mppi_status st = h->model->launchLinearize(a, h->stream, err);
   if (st != MPPI_OK)
     return fail(h, st, err);
+  return MPPI_OK;
+}
+
+/** the Jacobians into the caller's host arrays: one launch, two copies back, one synchronisation */
+static mppi_status linearizeOnDevice(mppi_handle h, const float* x_d, const float* u_d, int n, float* A_out, float* B_out)
+{
+  const size_t nA = (size_t)n * h->S * h->S, nB = (size_t)n * h->S * h->C;
+  kernels::LinearizeArgs a{};
+  MPPI_TRY(linearizeLaunch(h, x_d, u_d, n, a));
   HIP_TRY(h, hipMemcpyAsync(A_out, a.A_d, sizeof(float) * nA, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipMemcpyAsync(B_out, a.B_d, sizeof(float) * nB, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MPPI_OK;
+}
+
+/** the caller's points x[n][S], u[n][C] -> h->lin_in_d, queued on the stream */
+static mppi_status uploadPoints(mppi_handle h, const float* x, const float* u, int n)
+{
+  const size_t nx = (size_t)n * h->S, nu = (size_t)n * h->C;
+  if (h->lin_in_d.size() < nx + nu)
+  {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, h->lin_in_d.alloc(nx + nu));
+  }
+  HIP_TRY(h, hipMemcpyAsync(h->lin_in_d, x, sizeof(float) * nx, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->lin_in_d + nx, u, sizeof(float) * nu, hipMemcpyHostToDevice, h->stream));
   return MPPI_OK;
 }
 
@@ -872,29 +895,21 @@ mppi_status mppi_linearize(mppi_handle h, const float* x, const float* u, int n,
   if (!h->model->hasComputeGrad())
     return fail(h, MPPI_ERR_UNSUPPORTED, "mppi_linearize: the Dynamics class of model '" + h->model_name + "' declares no computeGrad");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  const size_t nx = (size_t)n * h->S, nu = (size_t)n * h->C;
-  if (h->lin_in_d.size() < nx + nu)
-  {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, h->lin_in_d.alloc(nx + nu));
-  }
-  HIP_TRY(h, hipMemcpyAsync(h->lin_in_d, x, sizeof(float) * nx, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(h->lin_in_d + nx, u, sizeof(float) * nu, hipMemcpyHostToDevice, h->stream));
-  return linearizeOnDevice(h, h->lin_in_d, h->lin_in_d + nx, n, A_out, B_out);
+  MPPI_TRY(uploadPoints(h, x, u, n));
+  return linearizeOnDevice(h, h->lin_in_d, h->lin_in_d + (size_t)n * h->S, n, A_out, B_out);
 }
 
-mppi_status mppi_linearize_trajectory(mppi_handle h, int system, float* A_out, float* B_out)
+/** the (state, control) sequence of `system` where the last mppi_compute_control left it on the device, after the refusals
+ *  mppi_linearize_trajectory and mppi_compute_feedback share; `who` names the entry point in the message */
+static mppi_status trajectoryPoints(mppi_handle h, const char* who, int system, const float*& x_d, const float*& u_d)
 {
-  CHECK_HANDLE(h);  // (split hand-over: behind the trajectory phase that writes the state sequence)
-  if (!A_out || !B_out)
-    return fail(h, MPPI_ERR_INVALID_ARG, "mppi_linearize_trajectory: null pointer");
   if (!h->model->hasComputeGrad())
     return fail(h, MPPI_ERR_UNSUPPORTED,
-                "mppi_linearize_trajectory: the Dynamics class of model '" + h->model_name + "' declares no computeGrad");
+                std::string(who) + ": the Dynamics class of model '" + h->model_name + "' declares no computeGrad");
   if (system != 0 && !(system == 1 && h->D == 2))
-    return fail(h, MPPI_ERR_INVALID_ARG, "mppi_linearize_trajectory: system 0, or 1 (the nominal system) on a Tube / Robust handle");
+    return fail(h, MPPI_ERR_INVALID_ARG, std::string(who) + ": system 0, or 1 (the nominal system) on a Tube / Robust handle");
   if (!h->have_result)
-    return fail(h, MPPI_ERR_STATE, "mppi_linearize_trajectory: no mppi_compute_control has run on this handle yet");
+    return fail(h, MPPI_ERR_STATE, std::string(who) + ": no mppi_compute_control has run on this handle yet");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   // which system of the last finalize pass holds the sequence a getter reports: through the system table, as the getters do
   const std::vector<float>* xs = system == 0 ? h->sys.state[0] : &h->nominal_state_h;
@@ -909,9 +924,138 @@ mppi_status mppi_linearize_trajectory(mppi_handle h, int system, float* A_out, f
   }
   const int T = h->cfg.num_timesteps;
   float* base = h->results_in_io ? h->io_out_h.dev() : h->out_block_d.get();
-  const float* x_d = outSlice(base, h->out.state) + (size_t)zx * T * h->S;
-  const float* u_d = outSlice(base, h->out.control) + (size_t)zu * h->TC;
-  return linearizeOnDevice(h, x_d, u_d, T, A_out, B_out);
+  x_d = outSlice(base, h->out.state) + (size_t)zx * T * h->S;
+  u_d = outSlice(base, h->out.control) + (size_t)zu * h->TC;
+  return MPPI_OK;
+}
+
+mppi_status mppi_linearize_trajectory(mppi_handle h, int system, float* A_out, float* B_out)
+{
+  CHECK_HANDLE(h);  // (split hand-over: behind the trajectory phase that writes the state sequence)
+  if (!A_out || !B_out)
+    return fail(h, MPPI_ERR_INVALID_ARG, "mppi_linearize_trajectory: null pointer");
+  const float *x_d = nullptr, *u_d = nullptr;
+  MPPI_TRY(trajectoryPoints(h, "mppi_linearize_trajectory", system, x_d, u_d));
+  return linearizeOnDevice(h, x_d, u_d, h->cfg.num_timesteps, A_out, B_out);
+}
+
+/* ---------------------------------------------------------------- DDP tracking gains ----------------------------- */
+mppi_status mppi_set_feedback_params(mppi_handle h, const float* Q, const float* R, const float* Qf, int num_iterations)
+{
+  CHECK_HANDLE_HOST(h);
+  if (num_iterations != 1)
+    return fail(h, MPPI_ERR_UNSUPPORTED,
+                "mppi_set_feedback_params: num_iterations = " + std::to_string(num_iterations) +
+                    " needs the forward pass and line search of the reference's DDP (ddp/ddp.h:129-162), which are not built; "
+                    "only the backward pass of num_iterations = 1 (the DDPParams default) is");
+  const int S = h->S, C = h->C;
+  std::vector<float>& p = h->fb_params_h;
+  p.assign((size_t)2 * S * S + C * C, 0.0f);
+  auto fill = [](float* dst, const float* src, int n) {
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < n; j++)
+        dst[i * n + j] = src ? src[i * n + j] : (i == j ? 1.0f : 0.0f);
+  };
+  fill(p.data(), Q, S);
+  fill(p.data() + S * S, R, C);
+  fill(p.data() + S * S + C * C, Qf, S);
+  h->fb_params_dirty = true;
+  return MPPI_OK;
+}
+
+/** linearizeKernel, then ddpBackwardKernel reading its A, B in place, on the handle's stream; the status and (gains_out != null)
+ *  the gains come back with one synchronisation.  install: a successful result becomes the model's gains, device to device. */
+static mppi_status feedbackOnDevice(mppi_handle h, const char* who, const float* x_d, const float* u_d, bool install,
+                                    float* gains_out)
+{
+  const int T = h->cfg.num_timesteps;
+  const size_t nG = (size_t)T * h->S * h->C, nSS = (size_t)h->S * h->S, nCC = (size_t)h->C * h->C;
+  if (h->fb_params_h.empty())
+    MPPI_TRY(mppi_set_feedback_params(h, nullptr, nullptr, nullptr, 1));  // DDPParams' defaults: identities
+  if (h->fb_gains_d.size() < nG || h->fb_params_d.size() < 2 * nSS + nCC || h->fb_status_d.size() < 2)
+  {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, h->fb_gains_d.alloc(nG));
+    HIP_TRY(h, h->fb_params_d.alloc(2 * nSS + nCC));
+    HIP_TRY(h, h->fb_status_d.alloc(2));
+    h->fb_params_dirty = true;
+  }
+  if (h->fb_params_dirty)
+  {
+    // pageable source: the copy has left fb_params_h when the call returns
+    HIP_TRY(h, hipMemcpyAsync(h->fb_params_d, h->fb_params_h.data(), sizeof(float) * (2 * nSS + nCC), hipMemcpyHostToDevice, h->stream));
+    h->fb_params_dirty = false;
+  }
+  kernels::LinearizeArgs lin{};
+  MPPI_TRY(linearizeLaunch(h, x_d, u_d, T, lin));
+  kernels::DdpBackwardArgs a{};
+  a.A_d = lin.A_d;
+  a.B_d = lin.B_d;
+  a.Q_d = h->fb_params_d;
+  a.R_d = h->fb_params_d + nSS;
+  a.Qf_d = h->fb_params_d + nSS + nCC;
+  a.gains_d = h->fb_gains_d;
+  a.status_d = h->fb_status_d;
+  a.dt = h->cfg.dt;
+  a.T = T;
+  std::string err;
+  mppi_status st = h->model->launchDdpBackward(a, h->stream, err);
+  if (st != MPPI_OK)
+    return fail(h, st, err);
+  int status[2] = { 0, 0 };
+  if (gains_out)
+  {
+    h->fb_gains_h.resize(nG);
+    HIP_TRY(h, hipMemcpyAsync(h->fb_gains_h.data(), a.gains_d, sizeof(float) * nG, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_TRY(h, hipMemcpyAsync(status, a.status_d, sizeof(status), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (status[0] != 1)
+    return fail(h, MPPI_ERR_NAN,
+                std::string(who) + ": the backward pass failed at step " + std::to_string(status[1]) +
+                    ": a pivot of quu = R dt + Bd^T Vxx Bd is not positive and finite; no gains were produced or installed");
+  if (gains_out)
+    std::copy(h->fb_gains_h.begin(), h->fb_gains_h.end(), gains_out);
+  if (install)
+  {
+    st = h->model->setFeedbackGains(h->fb_gains_d, T, h->fb_accumulate_all, true, h->stream, err);
+    if (st != MPPI_OK)
+      return fail(h, st, err);
+    h->gains_set = true;
+  }
+  return MPPI_OK;
+}
+
+mppi_status mppi_compute_feedback(mppi_handle h, int system, float* gains_out)
+{
+  CHECK_HANDLE(h);  // (split hand-over: behind the trajectory phase that writes the state sequence)
+  const bool robust_nominal = h->cfg.controller == MPPI_CONTROLLER_ROBUST && system == 1;
+  if (robust_nominal && !h->have_result && h->rm_traj_ready && h->model->hasComputeGrad())
+  {
+    // a Robust handle cannot run before it has gains: its first ones come from the nominal trajectory
+    // mppi_update_importance_sampling_control left on the host (where the reference calls computeNominalFeedbackGains)
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int T = h->cfg.num_timesteps;
+    MPPI_TRY(uploadPoints(h, h->nominal_state_h.data(), h->nominal_control_h.data(), T));
+    return feedbackOnDevice(h, "mppi_compute_feedback", h->lin_in_d, h->lin_in_d + (size_t)T * h->S, true, gains_out);
+  }
+  const float *x_d = nullptr, *u_d = nullptr;
+  MPPI_TRY(trajectoryPoints(h, "mppi_compute_feedback", system, x_d, u_d));
+  return feedbackOnDevice(h, "mppi_compute_feedback", x_d, u_d, robust_nominal, gains_out);
+}
+
+mppi_status mppi_compute_feedback_at(mppi_handle h, const float* x, const float* u, float* gains_out)
+{
+  CHECK_HANDLE(h);
+  if (!x || !u)
+    return fail(h, MPPI_ERR_INVALID_ARG, "mppi_compute_feedback_at: null pointer");
+  if (!h->model->hasComputeGrad())
+    return fail(h, MPPI_ERR_UNSUPPORTED,
+                "mppi_compute_feedback_at: the Dynamics class of model '" + h->model_name + "' declares no computeGrad");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  const int T = h->cfg.num_timesteps;
+  MPPI_TRY(uploadPoints(h, x, u, T));
+  return feedbackOnDevice(h, "mppi_compute_feedback_at", h->lin_in_d, h->lin_in_d + (size_t)T * h->S, false, gains_out);
 }
 
 mppi_status mppi_get_control_seq(mppi_handle h, float* u)
@@ -1089,7 +1233,7 @@ mppi_status mppi_set_feedback_gains(mppi_handle h, const float* gains, int accum
     return fail(h, MPPI_ERR_STATE, "mppi_set_feedback_gains: the handle is not a Robust MPPI controller");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   std::string err;
-  mppi_status st = h->model->setFeedbackGains(gains, h->cfg.num_timesteps, accumulate_all_states != 0, h->stream, err);
+  mppi_status st = h->model->setFeedbackGains(gains, h->cfg.num_timesteps, accumulate_all_states != 0, false, h->stream, err);
   if (st != MPPI_OK)
     return fail(h, st, err);
   h->gains_set = true;
@@ -1116,7 +1260,9 @@ mppi_status mppi_update_importance_sampling_control(mppi_handle h, const float* 
   std::vector<float> zero(C);
   h->model->getZeroControl(zero.data());
   slideSequence(h->nominal_control_h, T, C, h->nominal_stride, zero.data(), h->slide_scale_h.data());
-  return rmNominalStateTrajectory(h);
+  MPPI_TRY(rmNominalStateTrajectory(h));
+  h->rm_traj_ready = true;
+  return MPPI_OK;
 }
 
 mppi_status mppi_get_rmppi_state(mppi_handle h, float* nominal_state, int* best_index, int* nominal_stride,

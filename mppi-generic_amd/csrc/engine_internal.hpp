@@ -230,6 +230,13 @@ struct mppi_handle_s
   bool have_result = false;        // a mppi_compute_control has succeeded: the out block / outbox holds its sequences
   HipBuffer<float> lin_in_d;       // mppi_linearize: the caller's points [n][S] | [n][C]
   HipBuffer<float> lin_out_d;      // mppi_linearize / mppi_linearize_trajectory: A [n][S][S] | B [n][S][C]
+  /* mppi_set_feedback_params / mppi_compute_feedback[_at] (engine/feedback_kernel.hpp) */
+  std::vector<float> fb_params_h;  // Q [S][S] | R [C][C] | Qf [S][S]; empty: never set (identities on first use)
+  bool fb_params_dirty = false;    // fb_params_h is newer than fb_params_d
+  HipBuffer<float> fb_params_d;    // the same on the device
+  HipBuffer<float> fb_gains_d;     // ddpBackwardKernel's gains [T][S][C]
+  HipBuffer<int> fb_status_d;      // its status { ok, failing step }
+  std::vector<float> fb_gains_h;   // the gains on their way to the caller: handed over only when the pass succeeded
   bool out_pin_fresh = false;      // out_pin_h holds the results (incl. stats) of the last finalize pass; reset by launches
   bool stats_h_fresh = false;      // stats_h IS the statistics of the last merge (parsed at a low-latency hand-over); reset by launches
   HipBuffer<float> step_x_d;       // [S + C]
@@ -257,6 +264,7 @@ struct mppi_handle_s
   bool fb_accumulate_all = false;
   bool gains_set = false;
   bool rm_nominal_init = false;
+  bool rm_traj_ready = false;  // mppi_update_importance_sampling_control has left a nominal trajectory in nominal_state_h / nominal_control_h
   int best_index = 0, nominal_stride = 0, real_stride = 0;
   std::vector<float> rm_nominal_state, rm_line_weights, rm_cand_states, rm_cand_costs, rm_cand_free_energy,
       nominal_history_h;

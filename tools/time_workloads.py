@@ -13,7 +13,9 @@ autorally-robust: "autorally_nn_robust" (ARRobustCost on a four-channel 600 x 60
 K = 16384, T = 150 — the vanilla iteration on the default MFMA shape, fused and role-pipelined, and Robust MPPI's computeControl
 (wall clock around the call, which returns after the control is on the host) — each beside "autorally_nn" with ARStandardCost in
 the same run, as the yardstick; registration unit examples/autorally_robust_model/autorally_robust_model.hip, or an argument ending
-in .so)"""
+in .so)
+linearize / feedback: wall clock of mppi_linearize_trajectory / mppi_compute_feedback on Cartpole T = 100 and AutoRally-NN T = 150;
+not part of the default set.)"""
 import os
 import sys
 
@@ -172,4 +174,31 @@ if "linearize" in which:
         lin = timed(eng.computeGradTrajectory)
         print("%-10s K=%d T=%d computeControl %.1f us (p10 %.1f, p90 %.1f); linearize_trajectory %.1f us (p10 %.1f, p90 %.1f)"
               % ((name, cfg["K"], cfg["T"]) + tuple(cc) + tuple(lin)), flush=True)
+        eng.close()
+if "feedback" in which:
+    # mppi_compute_feedback (linearizeKernel + ddpBackwardKernel, the gains and the status back, one synchronisation) next to
+    # mppi_linearize_trajectory on the same handle: wall time of the whole call, median and p10 / p90 over 5000 calls after
+    # warm-up, as the linearize mode above.  The kernels' own times are not in these figures; take them from a kernel trace of
+    # this mode, in a run of its own.
+    import time  # noqa: E402
+    for name, cfg in (("cartpole", cartpole_cfg(K=16384, T=100)), ("autorally", autorally_cfg(K=16384, T=150, lambda_=1.0))):
+        eng = make_engine(cfg)
+        for _ in range(200):
+            eng.computeControl(cfg["x0"], 1)
+            eng.computeGradTrajectory()
+            eng.computeFeedback()
+
+        def timed(fn, n=5000):
+            t = []
+            for _ in range(n):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e6)
+            return np.percentile(t, [50, 10, 90])
+
+        eng.getTargetStateSeq()
+        lin = timed(eng.computeGradTrajectory)
+        fb = timed(eng.computeFeedback)
+        print("%-10s K=%d T=%d linearize_trajectory %.1f us (p10 %.1f, p90 %.1f); compute_feedback %.1f us (p10 %.1f, p90 %.1f)"
+              % ((name, cfg["K"], cfg["T"]) + tuple(lin) + tuple(fb)), flush=True)
         eng.close()
