@@ -33,8 +33,9 @@ extern "C" {
 #endif
 
 #define MPPI_AMD_VERSION_MAJOR 0
-#define MPPI_AMD_VERSION_MINOR 4 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory; 4: mppi_set_feedback_params,
-                                    mppi_compute_feedback, mppi_compute_feedback_at */
+#define MPPI_AMD_VERSION_MINOR 5 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory; 4: mppi_set_feedback_params,
+                                    mppi_compute_feedback, mppi_compute_feedback_at; 5: mppi_create_with_sampler takes
+                                    MPPI_CONTROLLER_TUBE with MPPI_SAMPLER_COLORED */
 
 typedef struct mppi_handle_s* mppi_handle;
 
@@ -179,9 +180,15 @@ const char* mppi_source_hash(void);
 typedef enum mppi_sampler_kind
 {
   MPPI_SAMPLER_GAUSSIAN = 0, /* used by the Vanilla / Tube / Robust controllers */
-  MPPI_SAMPLER_COLORED = 1,  /* used by MPPI_CONTROLLER_COLORED */
-  MPPI_SAMPLER_NLN = 2       /* normal-log-normal noise (log-MPPI; sampling_distributions/nln/nln.cuh), for the Vanilla / Tube /
+  MPPI_SAMPLER_COLORED = 1,  /* used by MPPI_CONTROLLER_COLORED; MPPI_CONTROLLER_TUBE takes it through mppi_create_with_sampler
+                              * (one colored draw per rollout for both systems; fused kernel only) */
+  MPPI_SAMPLER_NLN = 2,      /* normal-log-normal noise (log-MPPI; sampling_distributions/nln/nln.cuh), for the Vanilla / Tube /
                               * Robust controllers through mppi_create_with_sampler */
+  MPPI_SAMPLER_COLORED_TUBE = 3 /* a registry key, not a sampler of its own: the two-system instantiation of a model with the
+                              * colored-noise sampler, which mppi_create_with_sampler(cfg, MPPI_SAMPLER_COLORED) runs for
+                              * MPPI_CONTROLLER_TUBE.  For mppi_register_model*, mppi_unregister_model and mppi_describe_model;
+                              * mppi_create_with_sampler refuses it (MPPI_ERR_INVALID_ARG).  The registrations under
+                              * MPPI_SAMPLER_COLORED stay what MPPI_CONTROLLER_COLORED runs: one system */
 } mppi_sampler_kind;
 /** returns a new mppi::engine::ModelBase* (owned by the handle that asked for it) */
 typedef void* (*mppi_model_factory)(void);
@@ -229,8 +236,15 @@ mppi_status mppi_describe_model(const char* name, int sampler_kind, int* shapes,
 mppi_status mppi_create(const mppi_config* cfg, mppi_handle* out);
 /**
  * mppi_create with the sampling distribution named (the reference's SAMPLING_T template argument): the Vanilla, Tube and Robust
- * controllers take MPPI_SAMPLER_GAUSSIAN or MPPI_SAMPLER_NLN, MPPI_CONTROLLER_COLORED takes MPPI_SAMPLER_COLORED only; any
- * other combination is MPPI_ERR_INVALID_ARG, a (model, sampler) pair that is not registered MPPI_ERR_UNKNOWN_MODEL.
+ * controllers take MPPI_SAMPLER_GAUSSIAN or MPPI_SAMPLER_NLN, MPPI_CONTROLLER_COLORED takes MPPI_SAMPLER_COLORED only, and
+ * MPPI_CONTROLLER_TUBE takes MPPI_SAMPLER_COLORED too (the reference's TubeMPPIController with ColoredNoiseDistribution: one
+ * spectrum per rollout for both systems, injected as z[n_iters][K_local][C][T+1][2]; the fused rollout kernel only —
+ * MPPI_KERNEL_PIPELINE is MPPI_ERR_LAUNCH_SHAPE; mppi_set_independent_noise(h, 1) is MPPI_ERR_UNSUPPORTED).
+ * MPPI_CONTROLLER_ROBUST with MPPI_SAMPLER_COLORED is MPPI_ERR_UNSUPPORTED (its candidate evaluation needs a random-access
+ * draw the colored sampler does not have); any other combination is MPPI_ERR_INVALID_ARG, a (model, sampler) pair that is
+ * not registered MPPI_ERR_UNKNOWN_MODEL (MPPI_ERR_UNSUPPORTED for a model without a colored-noise instantiation).
+ * Tube with MPPI_SAMPLER_COLORED runs the model's registration under MPPI_SAMPLER_COLORED_TUBE; a model without one runs its
+ * MPPI_SAMPLER_COLORED registration if that lists a two-system shape (the templated controllers' do), else MPPI_ERR_LAUNCH_SHAPE.
  * mppi_create(cfg, out) is mppi_create_with_sampler(cfg, COLORED for MPPI_CONTROLLER_COLORED else GAUSSIAN, out).
  * NLN: eps' = z * exp(std_dev[c] * z') with z, z' from Philox streams s and 16 + s (mppi_amd/sampling_distributions/nln.hpp);
  * injected noise is taken as eps' itself; MPPI_NOISE_ROCRAND_HOST is refused with MPPI_ERR_UNSUPPORTED (the host generator
@@ -289,13 +303,15 @@ mppi_status mppi_set_cost_params(mppi_handle h, const void* pod, size_t nbytes);
 /** SamplingDistribution::setParams (sampling_distributions/sampling_distribution.cuh:93-116) */
 mppi_status mppi_set_sampler_params(mppi_handle h, const mppi_gaussian_params* p);
 /** ColoredNoiseParamsImpl (sampling_distributions/colored_noise/colored_noise.cuh:45-73): exponents[C] (0 = white),
- *  offset_decay_rate, fmin.  Only for handles created with MPPI_CONTROLLER_COLORED; std_dev etc. come from
+ *  offset_decay_rate, fmin.  Only for handles whose sampler is MPPI_SAMPLER_COLORED (MPPI_CONTROLLER_COLORED, or
+ *  MPPI_CONTROLLER_TUBE created with that sampler); std_dev etc. come from
  *  mppi_set_sampler_params as for the Gaussian sampler (ColoredNoiseParams extends GaussianParams). */
 /**
  * use_same_noise_for_all_distributions (sampling_distributions/sampling_distribution.cuh:20; gaussian.cu:378-394).  Default
  * (0): the systems of a Tube / Robust controller see the SAME noise, as the reference's default.  independent != 0: every
  * distribution draws its own — Philox stream d in the generator modes, slab d of the buffer for injected noise, which then is
- * eps[n_iters][D][K_local][T][C].
+ * eps[n_iters][D][K_local][T][C].  MPPI_ERR_UNSUPPORTED with independent != 0 on a handle whose sampler is
+ * MPPI_SAMPLER_COLORED: it draws one spectrum per rollout, no per-system spectrum stream is assigned.
  */
 mppi_status mppi_set_independent_noise(mppi_handle h, int independent);
 /**
@@ -395,7 +411,7 @@ mppi_status mppi_set_nominal_control(mppi_handle h, const float* u);
 mppi_status mppi_sample_noise(mppi_handle h, int optimization_stride, float* eps_out);
 /**
  * Parity / replay mode: eps[n_iters][K_local][T][C] replaces the generator for the next mppi_compute_control calls
- * (iteration i of a call uses slab i % n_iters).  MPPI_CONTROLLER_COLORED handles take the Gaussian SPECTRUM instead, in
+ * (iteration i of a call uses slab i % n_iters).  Handles with MPPI_SAMPLER_COLORED take the Gaussian SPECTRUM instead, in
  * the layout of the reference's samples_in_freq_complex_d_: z[n_iters][K_local][C][T+1][2] (colored_noise.cu:343).
  * Switches the handle to MPPI_NOISE_INJECTED.  n_iters == 0 switches
  * back to the configured generator.  (No reference equivalent: the reference never pins its noise)

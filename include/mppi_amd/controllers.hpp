@@ -384,7 +384,8 @@ public:
   }
 };
 
-/** reference: controllers/Tube-MPPI/tube_mppi_controller.cuh */
+/** reference: controllers/Tube-MPPI/tube_mppi_controller.cuh; sampler_kind: MPPI_SAMPLER_GAUSSIAN, _NLN, or _COLORED (the
+ *  reference's TubeMPPIController with ColoredNoiseDistribution as SAMPLING_T: one colored draw per rollout for both systems) */
 class TubeMPPIController : public Controller
 {
 public:
@@ -393,6 +394,11 @@ public:
     : Controller(model, MPPI_CONTROLLER_TUBE, num_rollouts, num_timesteps, dt, max_iter, lambda, alpha, seed, device, 0, 1, nullptr,
                  sampler_kind)
   {
+  }
+  /** for a controller created with MPPI_SAMPLER_COLORED (any other: MPPI_ERR_STATE) */
+  void setColoredNoiseParams(const std::vector<float>& exponents, float offset_decay_rate = 0.97f, float fmin = 0.0f)
+  {
+    check(mppi_set_colored_noise_params(h_, exponents.data(), offset_decay_rate, fmin));
   }
   void setNominalThreshold(float t)
   {

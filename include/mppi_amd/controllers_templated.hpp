@@ -480,7 +480,29 @@ protected:
       check(mppi_set_independent_noise(h_, sp.use_same_noise_for_all_distributions ? 0 : 1));
       std::memcpy((void*)&smp_params_, &sp, sizeof(sp));
     }
+    if constexpr (SAMPLING_T::COLORED)
+      syncColoredNoiseParams();  // whichever controller runs with ColoredNoiseDistribution: ColoredMPPI, or Tube
     pushed_ = true;
+  }
+  /** exponents, offset decay and fmin of a ColoredNoiseDistribution live in the caller's sampler object */
+  void syncColoredNoiseParams()
+  {
+    float ex[CONTROL_DIM];
+    bool changed = !colored_pushed_ || decay_ != sampler_->offset_decay_rate_ || fmin_ != sampler_->fmin_;
+    for (int i = 0; i < CONTROL_DIM; i++)
+    {
+      ex[i] = sampler_->exponents_[i];
+      changed = changed || ex[i] != ex_[i];
+    }
+    if (changed)
+    {
+      check(mppi_set_colored_noise_params(h_, ex, sampler_->offset_decay_rate_, sampler_->fmin_));
+      for (int i = 0; i < CONTROL_DIM; i++)
+        ex_[i] = ex[i];
+      decay_ = sampler_->offset_decay_rate_;
+      fmin_ = sampler_->fmin_;
+      colored_pushed_ = true;
+    }
   }
 
   PARAMS_T params_;
@@ -493,6 +515,9 @@ protected:
   alignas(8) unsigned char cost_params_[sizeof(typename COST_T::COST_PARAMS_T)];
   alignas(8) unsigned char smp_params_[sizeof(typename SAMPLING_T::SAMPLING_PARAMS_T)];
   float rng_[2 * DYN_T::CONTROL_DIM], db_[DYN_T::CONTROL_DIM];
+  bool colored_pushed_ = false;
+  float ex_[DYN_T::CONTROL_DIM] = {};
+  float decay_ = 0.0f, fmin_ = 0.0f;
 };
 }  // namespace templated
 }  // namespace mppi_amd
@@ -686,31 +711,7 @@ public:
   {
     return "Colored MPPI";
   }
-
-protected:
-  void syncPlugins() override
-  {
-    PARENT_CLASS::syncPlugins();
-    float ex[DYN_T::CONTROL_DIM];
-    bool changed = !colored_pushed_ || decay_ != this->sampler_->offset_decay_rate_ || fmin_ != this->sampler_->fmin_;
-    for (int i = 0; i < DYN_T::CONTROL_DIM; i++)
-    {
-      ex[i] = this->sampler_->exponents_[i];
-      changed = changed || ex[i] != ex_[i];
-    }
-    if (changed)
-    {
-      this->check(mppi_set_colored_noise_params(this->h_, ex, this->sampler_->offset_decay_rate_, this->sampler_->fmin_));
-      for (int i = 0; i < DYN_T::CONTROL_DIM; i++)
-        ex_[i] = ex[i];
-      decay_ = this->sampler_->offset_decay_rate_;
-      fmin_ = this->sampler_->fmin_;
-      colored_pushed_ = true;
-    }
-  }
-  bool colored_pushed_ = false;
-  float ex_[DYN_T::CONTROL_DIM] = {};
-  float decay_ = 0.0f, fmin_ = 0.0f;
+  // (the colored-noise parameters are pushed by ControllerBase::syncPlugins for every controller that runs with this sampler)
 };
 
 #undef MPPI_AMD_TPL_ARGS

@@ -416,7 +416,8 @@ class MPPIController:
                  noise_source=MPPI_NOISE_PHILOX_FUSED, block_x=0, block_y=0, device=0, stream=None, rank=0,
                  world_size=1, save_samples=False, kernel_variant=0, force_exchange=False, sampler=None):
         """sampler: an MPPI_SAMPLER_* constant, the reference's SAMPLING_T.  None is the controller's own (Gaussian; colored noise
-        for ColoredMPPIController); the Vanilla, Tube and Robust controllers also take MPPI_SAMPLER_NLN (log-MPPI)."""
+        for ColoredMPPIController); the Vanilla, Tube and Robust controllers also take MPPI_SAMPLER_NLN (log-MPPI), and
+        TubeMPPIController takes MPPI_SAMPLER_COLORED (one colored draw per rollout, shared by both systems)."""
         self._lib = load_library()
         self._h = C.c_void_p()
         self._model = model.encode()
@@ -580,8 +581,16 @@ class MPPIController:
         self._check(self._lib.mppi_inject_noise(self._h, eps.ctypes.data, eps.shape[0]))
 
     def _noise_shape(self):
+        if getattr(self, "sampler", MPPI_SAMPLER_GAUSSIAN) == MPPI_SAMPLER_COLORED:
+            # spectrum noise, the reference's samples_in_freq_complex_d_ layout: [K][C][T+1][2], one spectrum for every system
+            return (self.num_rollouts_local, self.CONTROL_DIM, self.num_timesteps + 1, 2)
         base = (self.num_rollouts_local, self.num_timesteps, self.CONTROL_DIM)
         return ((self.num_systems,) + base) if getattr(self, "_independent_noise", False) else base
+
+    def setColoredNoiseParams(self, exponents, offset_decay_rate=0.97, fmin=0.0):
+        """ColoredNoiseParams of a handle whose sampler is the colored-noise one (ColoredMPPIController, or
+        TubeMPPIController(..., sampler=MPPI_SAMPLER_COLORED)); MPPIError(MPPI_ERR_STATE) on any other"""
+        self._check(self._lib.mppi_set_colored_noise_params(self._h, _f32(exponents).reshape(-1), offset_decay_rate, fmin))
 
     def setIndependentNoise(self, independent=True):
         """use_same_noise_for_all_distributions = not independent (sampling_distribution.cuh:20); injected noise then is
@@ -821,18 +830,11 @@ class ColoredMPPIController(MPPIController):
     ColoredNoiseDistribution (sampling_distributions/colored_noise/colored_noise.cuh)"""
     KIND = MPPI_CONTROLLER_COLORED
 
-    def setColoredNoiseParams(self, exponents, offset_decay_rate=0.97, fmin=0.0):
-        self._check(self._lib.mppi_set_colored_noise_params(self._h, _f32(exponents).reshape(-1), offset_decay_rate, fmin))
-
     def setColoredMPPIParams(self, gamma=0.0, r_exp=0.0, state_leash_dist=None, leash_active=False, leash_jump=1):
         """setGamma / setRExp (Tsallis weights when both are non-zero) and the state leash (setStateLeashLength,
         setLeashActive; colored_mppi_controller.cuh:95-193)"""
         p = None if state_leash_dist is None else _f32(state_leash_dist).reshape(-1).ctypes.data
         self._check(self._lib.mppi_set_colored_mppi_params(self._h, gamma, r_exp, p, int(leash_active), leash_jump))
-
-    def _noise_shape(self):
-        """spectrum noise, the reference's samples_in_freq_complex_d_ layout: [K][C][T+1][2]"""
-        return (self.num_rollouts_local, self.CONTROL_DIM, self.num_timesteps + 1, 2)
 
 
 class RobustMPPIController(MPPIController):
@@ -899,6 +901,7 @@ KERNEL_FAMILIES = ("none", "fused", "fused_rep", "pipeline", "pipeline_fold", "p
 MPPI_SAMPLER_GAUSSIAN = 0
 MPPI_SAMPLER_COLORED = 1
 MPPI_SAMPLER_NLN = 2
+MPPI_SAMPLER_COLORED_TUBE = 3  # a registry key (describe_model): the two-system colored instantiation Tube runs
 _MODEL_CAPS = (("pipeline", 1), ("rmppi", 2), ("rmppi_pipeline", 4), ("rows_in_hbm", 8), ("streamed_merge", 16),
                ("pipeline_fold", 32))
 

@@ -34,14 +34,12 @@ static mppi_status checkArguments(const mppi_config* cfg, int sampler_kind, mppi
   if (!cfg || !out || !cfg->model)
     return fail(nullptr, MPPI_ERR_INVALID_ARG, "mppi_create: null argument");
   *out = nullptr;
-  {  // which sampler a controller kind takes (mppi_amd.h); an unknown controller kind is reported by the plan
-    const bool colored_ctl = cfg->controller == MPPI_CONTROLLER_COLORED;
-    const bool ok = colored_ctl ? sampler_kind == MPPI_SAMPLER_COLORED
-                                : (sampler_kind == MPPI_SAMPLER_GAUSSIAN || sampler_kind == MPPI_SAMPLER_NLN);
-    if (!ok)
-      return fail(nullptr, MPPI_ERR_INVALID_ARG,
-                  "mppi_create: the Vanilla, Tube and Robust controllers take MPPI_SAMPLER_GAUSSIAN or MPPI_SAMPLER_NLN, "
-                  "MPPI_CONTROLLER_COLORED takes MPPI_SAMPLER_COLORED only");
+  {  // which sampler a controller kind takes: the plan's rule (launch_plan.hpp), asked here so that a mismatch is reported
+     // before the sizes and before a device is looked for; an unknown controller kind is reported by the plan
+    std::string refusal;
+    const mppi_status rule = plan::samplerRule(cfg->controller, sampler_kind, &refusal);
+    if (rule != MPPI_OK)
+      return fail(nullptr, rule, refusal);
   }
   if (cfg->num_rollouts <= 0 || cfg->num_timesteps <= 0 || !(cfg->dt > 0.0f) || !(cfg->lambda > 0.0f) ||
       cfg->num_iters <= 0)
@@ -68,7 +66,13 @@ static mppi_status checkDevice(const mppi_config& cfg)
  *  itself rules out */
 static mppi_status resolveModel(const mppi_config& cfg, const std::string& name, int sampler_kind, std::unique_ptr<ModelBase>& model)
 {
-  model.reset(makeModel(name, sampler_kind));
+  // Tube with the colored sampler: the model's two-system registration; without one, its colored registration (the templated
+  // controllers list their two-system shapes there) — the plan then says whether that has a shape for two systems
+  const int key = plan::registrationKind(cfg.controller, sampler_kind);
+  if (key != sampler_kind)
+    model.reset(makeModel(name, key));
+  if (!model)
+    model.reset(makeModel(name, sampler_kind));
   const auto gaussianExists = [&] { return std::unique_ptr<ModelBase>(makeModel(name, MPPI_SAMPLER_GAUSSIAN)) != nullptr; };
   if (!model && sampler_kind == MPPI_SAMPLER_COLORED && gaussianExists())
     return fail(nullptr, MPPI_ERR_UNSUPPORTED, "mppi_create: model '" + name + "' has no colored-noise instantiation");
@@ -253,8 +257,7 @@ mppi_status mppi_create(const mppi_config* cfg, mppi_handle* out)
 {
   if (!cfg)
     return fail(nullptr, MPPI_ERR_INVALID_ARG, "mppi_create: null argument");
-  return mppi_create_with_sampler(cfg, cfg->controller == MPPI_CONTROLLER_COLORED ? MPPI_SAMPLER_COLORED : MPPI_SAMPLER_GAUSSIAN,
-                                  out);
+  return mppi_create_with_sampler(cfg, plan::defaultSampler(cfg->controller), out);
 }
 
 mppi_status mppi_create_with_sampler(const mppi_config* cfg, int sampler_kind, mppi_handle* out)
@@ -274,7 +277,7 @@ mppi_status mppi_create_with_sampler(const mppi_config* cfg, int sampler_kind, m
 
   LaunchPlan plan;
   std::string refusal;
-  const mppi_status planned = planLaunch(h->cfg, *h->model, sw.rows_in_hbm, &plan, &refusal);
+  const mppi_status planned = planLaunch(h->cfg, sampler_kind, *h->model, sw.rows_in_hbm, &plan, &refusal);
   if (planned != MPPI_OK)
     return fail(nullptr, planned, refusal);
   h->D = plan.D;

@@ -56,6 +56,55 @@ inline mppi_status refuse(std::string* err, mppi_status s, const std::string& ms
   return s;
 }
 
+/* ---------------------------------------------------------------- which sampler a controller kind takes -------------- */
+/** the sampler a controller kind runs with when none is named (mppi_create) */
+inline int defaultSampler(int controller)
+{
+  return controller == MPPI_CONTROLLER_COLORED ? MPPI_SAMPLER_COLORED : MPPI_SAMPLER_GAUSSIAN;
+}
+
+/** the registry key mppi_create looks a model up under first: Tube with the colored sampler has registrations of its own
+ *  (MPPI_SAMPLER_COLORED_TUBE), so that the ones under MPPI_SAMPLER_COLORED stay what MPPI_CONTROLLER_COLORED runs, one system */
+inline int registrationKind(int controller, int sampler_kind)
+{
+  return controller == MPPI_CONTROLLER_TUBE && sampler_kind == MPPI_SAMPLER_COLORED ? MPPI_SAMPLER_COLORED_TUBE : sampler_kind;
+}
+
+/** Vanilla, Tube and Robust take the Gaussian or the NLN sampler, MPPI_CONTROLLER_COLORED the colored one — and so does Tube:
+ *  the colored prologue writes one draw into the rows of both systems (the reference's use_same_noise_for_all_distributions).
+ *  Robust MPPI evaluates its candidates with draws addressed one by one; the colored rows exist only as the result of a
+ *  block-wide GEMM.  An unknown controller kind passes: the plan reports it. */
+inline mppi_status samplerRule(int controller, int sampler_kind, std::string* err)
+{
+  const bool colored = sampler_kind == MPPI_SAMPLER_COLORED;
+  if (controller == MPPI_CONTROLLER_TUBE && colored)
+    return MPPI_OK;
+  if (controller == MPPI_CONTROLLER_ROBUST && colored)
+    return refuse(err, MPPI_ERR_UNSUPPORTED,
+                  "mppi_create: Robust MPPI with MPPI_SAMPLER_COLORED is not available: its candidate evaluation draws single "
+                  "samples by index (random access), the colored-noise rows come out of a block-wide GEMM prologue and have no "
+                  "such draw");
+  const bool ok = controller == MPPI_CONTROLLER_COLORED ? colored :
+                                                          (sampler_kind == MPPI_SAMPLER_GAUSSIAN || sampler_kind == MPPI_SAMPLER_NLN);
+  if (!ok)
+    return refuse(err, MPPI_ERR_INVALID_ARG,
+                  "mppi_create: the Vanilla, Tube and Robust controllers take MPPI_SAMPLER_GAUSSIAN or MPPI_SAMPLER_NLN, "
+                  "MPPI_CONTROLLER_COLORED takes MPPI_SAMPLER_COLORED only");
+  return MPPI_OK;
+}
+
+/** mppi_set_independent_noise(h, 1): the colored-noise sampler draws one spectrum per rollout, whatever the controller */
+inline mppi_status independentNoiseRule(int controller, int sampler_kind, std::string* err)
+{
+  if (controller == MPPI_CONTROLLER_COLORED)
+    return refuse(err, MPPI_ERR_UNSUPPORTED, "independent noise per distribution: the colored-noise sampler has one distribution");
+  if (sampler_kind == MPPI_SAMPLER_COLORED)
+    return refuse(err, MPPI_ERR_UNSUPPORTED,
+                  "independent noise per distribution: the colored-noise sampler draws one spectrum per rollout for both systems "
+                  "of a Tube handle; no per-system spectrum stream is assigned");
+  return MPPI_OK;
+}
+
 /** an LDS-size query answered as if the sample rows were in HBM: the samplers drop their row term while their row pointer is
  *  set, so a placeholder stands in for the buffer mppi_create allocates later — for the length of the query only */
 template <class F>
@@ -137,10 +186,18 @@ inline mppi_status planRobust(const mppi_config& cfg, ModelBase& m, bool hbm_for
 }
 
 /* ---------------------------------------------------------------- Vanilla, Colored, Tube ----------------------------- */
-/** the shape runs as a rollout kernel of the model: a registered shape, or the folded pipeline's */
-inline bool instantiated(const ModelBase& m, Block b, int bz)
+/** the shape runs as a rollout kernel of the model: a registered shape, or — where the plan offers the role-pipelined forms
+ *  (`offered`: pipelinedFormsOffered) — the folded pipeline's */
+inline bool instantiated(const ModelBase& m, Block b, int bz, bool offered = true)
 {
-  return m.supportsShape(b.bx, b.by, bz) || m.supportsPipelineFold(b.bx, b.by, bz);
+  return m.supportsShape(b.bx, b.by, bz) || (offered && m.supportsPipelineFold(b.bx, b.by, bz));
+}
+
+/** Tube with the colored-noise sampler runs the fused kernel only: no role-pipelined or folded kernel has been held to the
+ *  oracle with the GEMM prologue filling the rows of two systems */
+inline bool pipelinedFormsOffered(const mppi_config& cfg, int sampler_kind)
+{
+  return !(cfg.controller == MPPI_CONTROLLER_TUBE && sampler_kind == MPPI_SAMPLER_COLORED);
 }
 
 /** Tube with a fold-capable model, no shape requested and not FUSED: the two systems in the lanes of a wave, (32, 1, 2) */
@@ -153,9 +210,9 @@ inline bool tubeFolds(const mppi_config& cfg, ModelBase& m)
 /** no shape requested and the model's default has no instantiation for bz systems (a Tube controller on a model whose default
  *  exists for bz = 1 only): the registered shape for bz with the default's lanes per rollout if there is one, otherwise the
  *  first one listed (replicated-lane shapes come first); the default itself when nothing is registered for bz */
-inline Block defaultBlockFor(const ModelBase& m, Block dflt, int bz)
+inline Block defaultBlockFor(const ModelBase& m, Block dflt, int bz, bool offered = true)
 {
-  if (instantiated(m, dflt, bz))
+  if (instantiated(m, dflt, bz, offered))
     return dflt;
   std::vector<int> shapes;
   m.listShapes(shapes);
@@ -211,17 +268,26 @@ inline Form largestFittingShape(ModelBase& m, const Form& f, int bz, int T, int 
   return best;
 }
 
-inline mppi_status planRollout(const mppi_config& cfg, ModelBase& m, bool hbm_forced, LaunchPlan* out, std::string* err)
+inline mppi_status planRollout(const mppi_config& cfg, ModelBase& m, bool hbm_forced, bool offered, LaunchPlan* out, std::string* err)
 {
   const int T = cfg.num_timesteps, D = out->D, bz = out->bz;
-  const Block block = tubeFolds(cfg, m) ? Block{ 32, 1 } :
-                      unshaped(cfg)     ? defaultBlockFor(m, requestedBlock(cfg, m), bz) :
-                                          requestedBlock(cfg, m);
-  if (!instantiated(m, block, bz))
+  const Block block = offered && tubeFolds(cfg, m) ? Block{ 32, 1 } :
+                      unshaped(cfg)                ? defaultBlockFor(m, requestedBlock(cfg, m), bz, offered) :
+                                                     requestedBlock(cfg, m);
+  if (!instantiated(m, block, bz, offered))
     return refuse(err, MPPI_ERR_LAUNCH_SHAPE,
                   "mppi_create: block shape (" + std::to_string(block.bx) + "," + std::to_string(block.by) + "," +
                       std::to_string(bz) + ") is not instantiated for model '" + cfg.model + "'");
-  const bool pipe_ok = pipelineEligible(m, block, bz);
+  if (!offered && !(block.bx == 64 && block.by == 1))
+    return refuse(err, MPPI_ERR_LAUNCH_SHAPE,
+                  "mppi_create: the Tube controller with MPPI_SAMPLER_COLORED runs block shape (64,1,2) only — the one shape whose "
+                  "prologue has been held to the oracle with two systems; (" + std::to_string(block.bx) + "," +
+                      std::to_string(block.by) + "," + std::to_string(bz) + ") was asked for");
+  if (cfg.kernel_variant == MPPI_KERNEL_PIPELINE && !offered)
+    return refuse(err, MPPI_ERR_LAUNCH_SHAPE,
+                  "mppi_create: the pipeline variant has no form for the Tube controller with MPPI_SAMPLER_COLORED; it runs the "
+                  "fused kernel (MPPI_KERNEL_AUTO or MPPI_KERNEL_FUSED)");
+  const bool pipe_ok = offered && pipelineEligible(m, block, bz);
   if (cfg.kernel_variant == MPPI_KERNEL_PIPELINE && !pipe_ok)
     return refuse(err, MPPI_ERR_LAUNCH_SHAPE,
                   "mppi_create: the pipeline variant needs a model registered for it and block shape (64, 1), or (64, REP, 1) "
@@ -242,7 +308,7 @@ inline mppi_status planRollout(const mppi_config& cfg, ModelBase& m, bool hbm_fo
     f = rowsInLds(false);  // the output ring does not fit next to the sample rows: the fused kernel
   if (!f.rows_in_hbm && (!f.fits() || hbm_forced) && cfg.kernel_variant != MPPI_KERNEL_PIPELINE && hbm_rows)
     f = fusedRowsInHbm(cfg, m, f, bz, D);
-  if (!f.fits() && unshaped(cfg) && cfg.kernel_variant != MPPI_KERNEL_PIPELINE)
+  if (!f.fits() && unshaped(cfg) && cfg.kernel_variant != MPPI_KERNEL_PIPELINE && offered)  // (Tube + colored keeps (64, 1, 2))
     f = largestFittingShape(m, f, bz, T, D);
   out->bx = f.block.bx;
   out->by = f.block.by;
@@ -253,11 +319,17 @@ inline mppi_status planRollout(const mppi_config& cfg, ModelBase& m, bool hbm_fo
 }
 }  // namespace plan
 
-/** The launch plan of a handle, or the refusal (status returned, text in *err; *out is unspecified then).  Leaves the model's
- *  row pointer null: mppi_create sets it once the buffer exists. */
-inline mppi_status planLaunch(const mppi_config& cfg, ModelBase& model, bool hbm_forced, LaunchPlan* out, std::string* err)
+/** The launch plan of a handle for the sampler kind of its model instantiation, or the refusal (status returned, text in *err;
+ *  *out is unspecified then).  Leaves the model's row pointer null: mppi_create sets it once the buffer exists. */
+inline mppi_status planLaunch(const mppi_config& cfg, int sampler_kind, ModelBase& model, bool hbm_forced, LaunchPlan* out,
+                              std::string* err)
 {
   *out = LaunchPlan();
+  {
+    const mppi_status rule = plan::samplerRule(cfg.controller, sampler_kind, err);
+    if (rule != MPPI_OK)
+      return rule;
+  }
   const bool robust = cfg.controller == MPPI_CONTROLLER_ROBUST;
   switch (cfg.controller)
   {
@@ -273,7 +345,8 @@ inline mppi_status planLaunch(const mppi_config& cfg, ModelBase& model, bool hbm
   }
   out->bz = out->D;
   // (Robust MPPI's two kernels are instantiated per model — checked above — not per block shape)
-  const mppi_status st = robust ? plan::planRobust(cfg, model, hbm_forced, out, err) : plan::planRollout(cfg, model, hbm_forced, out, err);
+  const mppi_status st = robust ? plan::planRobust(cfg, model, hbm_forced, out, err) :
+                                 plan::planRollout(cfg, model, hbm_forced, plan::pipelinedFormsOffered(cfg, sampler_kind), out, err);
   if (st != MPPI_OK)
     return st;
   if (out->lds > MAX_LDS_BYTES)
@@ -283,6 +356,12 @@ inline mppi_status planLaunch(const mppi_config& cfg, ModelBase& model, bool hbm
                             "controller / kernel variant has no rows-in-HBM form; shorten the horizon or register a block shape "
                             "with fewer rollouts");
   return MPPI_OK;
+}
+
+/** ... with the sampler the controller kind runs with when none is named */
+inline mppi_status planLaunch(const mppi_config& cfg, ModelBase& model, bool hbm_forced, LaunchPlan* out, std::string* err)
+{
+  return planLaunch(cfg, plan::defaultSampler(cfg.controller), model, hbm_forced, out, err);
 }
 
 }  // namespace engine

@@ -24,3 +24,10 @@ using CartpoleColoredModel =
     ModelT<CartpoleDynamics, CartpoleQuadraticCost, sampling_distributions::ColoredNoiseDistribution<CartpoleDynamicsParams>,
            Shapes<Shape<64, 1, 1>, Shape<64, 4, 1>>, /*FIN_BY=*/1, void, Shapes<>, /*PIPELINE=*/true>;
 MPPI_REGISTER_MODEL("cartpole", MPPI_SAMPLER_COLORED, CartpoleColoredModel, 64, 1)
+
+/* Tube with colored noise: one draw per rollout in the rows of both systems, the fused kernel only — a registration of its own,
+ * MPPI_CONTROLLER_COLORED's above stays one-system */
+using CartpoleColoredTubeModel =
+    ModelT<CartpoleDynamics, CartpoleQuadraticCost, sampling_distributions::ColoredNoiseDistribution<CartpoleDynamicsParams>,
+           Shapes<Shape<64, 1, 2>>, /*FIN_BY=*/1, void, Shapes<>, /*PIPELINE=*/false>;
+MPPI_REGISTER_MODEL("cartpole", MPPI_SAMPLER_COLORED_TUBE, CartpoleColoredTubeModel, 64, 1)

@@ -23,3 +23,11 @@ using DIColoredModel =
            sampling_distributions::ColoredNoiseDistribution<DoubleIntegratorParams>, Shapes<Shape<64, 1, 1>>, /*FIN_BY=*/1,
            void, Shapes<>, /*PIPELINE=*/true>;
 MPPI_REGISTER_MODEL("double_integrator", MPPI_SAMPLER_COLORED, DIColoredModel, 64, 1)
+
+/* Tube with colored noise (TubeMPPIController with ColoredNoiseDistribution as SAMPLING_T): one draw per rollout in the rows of
+ * both systems, the fused kernel only — a registration of its own, MPPI_CONTROLLER_COLORED's above stays one-system */
+using DIColoredTubeModel =
+    ModelT<DoubleIntegratorDynamics, DoubleIntegratorCircleCost,
+           sampling_distributions::ColoredNoiseDistribution<DoubleIntegratorParams>, Shapes<Shape<64, 1, 2>>, /*FIN_BY=*/1,
+           void, Shapes<>, /*PIPELINE=*/false>;
+MPPI_REGISTER_MODEL("double_integrator", MPPI_SAMPLER_COLORED_TUBE, DIColoredTubeModel, 64, 1)

@@ -26,12 +26,14 @@ import numpy as np  # noqa: E402
 from common import autorally_cfg, bicycle_lstm_cfg, cartpole_cfg, di_cfg, make_engine  # noqa: E402
 
 
-def run(name, cfg, shapes, n=100, **kw):
+def run(name, cfg, shapes, n=100, setup=None, **kw):
     for sh in shapes:
         bx, by = sh[0], sh[1]
         variant = sh[2] if len(sh) > 2 else 0
         try:
             eng = make_engine(cfg, block_x=bx, block_y=by, kernel_variant=variant, **kw)
+            if setup:
+                setup(eng)
         except Exception as e:  # noqa: BLE001
             print(name, (bx, by), "skip:", e)
             continue
@@ -61,6 +63,8 @@ if "autorally" in which:
     run("autorally", autorally_cfg(K=16384, T=150, lambda_=1.0), [(0, 0, 1), (0, 0, 2), (32, 4), (32, 8)], n=30)
 if "di" in which:
     run("di-tube", di_cfg(K=8192, T=150, tube=True), [(64, 1, 1), (0, 0, 0), (32, 1, 2)])
+    # Tube with colored noise: the fused (64, 1, 2) kernel (at T = 150 the rows of 2 x 64 slots go to HBM), beside the Gaussian lines above
+    run("di-tube+colored", di_cfg(K=8192, T=150, tube=True), [(64, 1, 1)], sampler=1, setup=lambda e: e.setColoredNoiseParams([1.0, 1.0]))
 if "lstm" in which:
     cfg = bicycle_lstm_cfg(K=65536, T=200, lambda_=1.0)
     run("lstm", cfg, [(0, 0, 1), (0, 0, 2)], n=10)
