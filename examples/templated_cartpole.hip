@@ -62,6 +62,7 @@ int main(int argc, char** argv)
   controller_params.dynamics_rollout_dim_ = dim3(64, lanes, 1);
   controller_params.cost_rollout_dim_ = dim3(64, lanes, 1);
   controller.setParams(controller_params);
+  controller.setTopNSampledControlTrajectories(3);  // (before the first use: the handle then keeps its samples)
 
   CartpoleDynamics::state_array x = CartpoleDynamics::state_array::Zero(), x_next = x, xdot = x;
   CartpoleDynamics::output_array y = CartpoleDynamics::output_array::Zero();
@@ -88,5 +89,16 @@ int main(int argc, char** argv)
     sum += u_seq(0, t);
   printf("%s: %d control steps in %.1f ms, pole angle %.4f rad, checksum %.6f\n", controller.getControllerName().c_str(), steps,
          ms, x[2], sum);
+  if (steps > 0)
+  {
+    // what the best rollouts of the last iteration did: row 0 is the optimal sequence, rows 1.. the three lowest-cost rollouts
+    controller.calculateSampledStateTrajectories();
+    const int O = CartpoleDynamics::OUTPUT_DIM;
+    const float* y_end = controller.getSampledOutputTrajectories().data() + ((size_t)1 * HORIZON + (HORIZON - 1)) * O;
+    printf("best rollout %d: cost %.3f, final output", controller.getSampledTrajectoryIndices()[1], controller.getTopNCosts()[0]);
+    for (int i = 0; i < O; i++)
+      printf(" %.4f", y_end[i]);
+    printf("\n");
+  }
   return 0;
 }

@@ -33,9 +33,9 @@ extern "C" {
 #endif
 
 #define MPPI_AMD_VERSION_MAJOR 0
-#define MPPI_AMD_VERSION_MINOR 5 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory; 4: mppi_set_feedback_params,
+#define MPPI_AMD_VERSION_MINOR 6 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory; 4: mppi_set_feedback_params,
                                     mppi_compute_feedback, mppi_compute_feedback_at; 5: mppi_create_with_sampler takes
-                                    MPPI_CONTROLLER_TUBE with MPPI_SAMPLER_COLORED */
+                                    MPPI_CONTROLLER_TUBE with MPPI_SAMPLER_COLORED; 6: mppi_top_rollouts, mppi_replay_rollouts */
 
 typedef struct mppi_handle_s* mppi_handle;
 
@@ -448,6 +448,43 @@ mppi_status mppi_get_costs(mppi_handle h, float* costs);
 mppi_status mppi_get_stats(mppi_handle h, mppi_stats* out);
 /** clamped samples v[D][K_local][T][C] of the last iteration (control_samples_d_); needs cfg.save_samples */
 mppi_status mppi_get_sampled_controls(mppi_handle h, float* v);
+
+/* ---------------------------------------------------------------- sampled rollouts, replayed ---------------------- */
+/* What the sampled rollouts of the last iteration did — the reference's Controller::setTopNSampledControlTrajectories /
+ * setPercentageSampledControlTrajectories / calculateSampledStateTrajectories and its getSampled{Output,Cost,CrashStatus}
+ * Trajectories / getTopNCosts (controllers/controller.cuh:229-296, 724-778; visualizeKernel, core/mppi_common.cu:364-525).
+ * Both calls run on the device, on the handle's stream behind whatever is queued there, and return after one synchronisation;
+ * nothing the controller computes depends on them.  `system` follows mppi_linearize_trajectory: 0, or 1 (the nominal system) on a
+ * Tube / Robust handle, anything else MPPI_ERR_INVALID_ARG.  Indices are LOCAL rollouts, [0, K_local) (mppi_get_local_rollouts). */
+/**
+ * The n lowest-cost rollouts of the last rollout launch of `system`, selected from the K_local trajectory costs where the kernel
+ * left them (mppi_amd/engine/top_rollouts_kernel.hpp: one block, radix select over order-preserving keys).  Ascending cost, ties
+ * to the lower index, NaN costs after every number.  idx_out[n] local indices, cost_out[n] the costs as mppi_get_costs gives them
+ * — raw, where the reference's getTopNCosts divides by the normaliser and leaves the order to its host list; either may be NULL.
+ * 1 <= n <= min(K_local, 256), else MPPI_ERR_INVALID_ARG; MPPI_ERR_STATE before the handle's first iteration.
+ */
+mppi_status mppi_top_rollouts(mppi_handle h, int system, int n, int* idx_out, float* cost_out);
+/**
+ * n rows run again from the initial state the last mppi_compute_control / mppi_rollout_costs / mppi_optimize left on the device
+ * for `system`, with the plugin calls of the rollout kernel in its order (mppi_amd/engine/replay_kernel.hpp, one launch in the lane
+ * form of the model's trajectory re-roll).  Row i is
+ *   rollout_idx[i] >= 0    row [system][idx] of the saved samples: needs cfg.save_samples (else MPPI_ERR_STATE, as
+ *                          mppi_get_sampled_controls);
+ *   rollout_idx[i] == -1   the control sequence mppi_get_control_seq (system 1: mppi_get_nominal_control_seq) returned after the
+ *                          last mppi_compute_control, where the device left it (the reference's slot 0); needs no saved samples,
+ *                          MPPI_ERR_STATE before the first mppi_compute_control.
+ * Kept per row, any of the three may be NULL:
+ *   y_out[n][T][O]            the output after step t (row t of mppi_get_output_seq is the output BEFORE step t: shifted by one)
+ *   step_cost_out[n][T + 1]   computeRunningCost + computeLikelihoodRatioCost of step t; entry T is terminalCost, undivided —
+ *                             summed over t in order, plus entry T, each sum divided by T, this is the rollout's trajectory cost
+ *   crash_out[n][T]           the crash status after step t
+ * The likelihood-ratio term reads the control mean that is on the device now: the rollouts' own after mppi_rollout_costs, the
+ * updated one after mppi_compute_control / mppi_optimize.  A model with a control deadband constrains a saved row a second time.
+ * 1 <= n <= 1024 and every index in [-1, K_local), else MPPI_ERR_INVALID_ARG; MPPI_ERR_STATE before the handle's first
+ * iteration; MPPI_ERR_UNSUPPORTED on a Robust handle (its real system's rollouts carry the feedback term).
+ */
+mppi_status mppi_replay_rollouts(mppi_handle h, int system, const int* rollout_idx, int n, float* y_out, float* step_cost_out,
+                                 int* crash_out);
 
 /* ---------------------------------------------------------------- linearisation ---------------------------------- */
 /* The continuous-time Jacobians of the model, A = d xdot / d x [S][S] and B = d xdot / d u [S][C], both row-major

@@ -26,6 +26,7 @@
 
 #include "mppi_amd.h"
 #include "mppi_amd/model_params.h"
+#include "mppi_amd/sampled_trajectories.hpp"
 
 namespace mppi_amd
 {
@@ -44,7 +45,7 @@ class Controller
 public:
   Controller(const std::string& model, int controller_kind, int num_rollouts, int num_timesteps, float dt, int max_iter,
              float lambda, float alpha, unsigned long long seed = 42, int device = 0, int rank = 0, int world_size = 1,
-             void* stream = nullptr, int sampler_kind = -1)
+             void* stream = nullptr, int sampler_kind = -1, bool save_samples = false)
     : num_rollouts_(num_rollouts), num_timesteps_(num_timesteps), dt_(dt)
   {
     mppi_config cfg{};
@@ -62,6 +63,7 @@ public:
     cfg.stream = stream;
     cfg.rank = rank;
     cfg.world_size = world_size;
+    cfg.save_samples = save_samples ? 1 : 0;  // what calculateSampledStateTrajectories replays rollouts from
     // sampler_kind < 0: the controller kind's own sampler (Gaussian; colored noise for MPPI_CONTROLLER_COLORED)
     const mppi_status s = sampler_kind < 0 ? mppi_create(&cfg, &h_) : mppi_create_with_sampler(&cfg, sampler_kind, &h_);
     if (s != MPPI_OK)
@@ -242,6 +244,55 @@ public:
   {
     return getFreeEnergyStatistics().real_sys.normalizer;
   }
+  /* ---- what the sampled rollouts did (sampled_trajectories.hpp; reference: controller.cuh:229-296, 724-778) ---- */
+  /** the N lowest-cost rollouts of the last iteration join the replayed rows (N <= 256) */
+  void setTopNSampledControlTrajectories(int n)
+  {
+    sampled_.top_n = n;
+  }
+  /** int(fraction * K) rollouts drawn without replacement from the first 98 % join them */
+  void setPercentageSampledControlTrajectories(float fraction)
+  {
+    sampled_.fraction = fraction;
+  }
+  void setSampledTrajectoriesSeed(unsigned long long seed)
+  {
+    sampled_.seed = seed;
+  }
+  int getTotalSampledTrajectories() const
+  {
+    return (int)sampled_.indices.size();
+  }
+  const std::vector<int>& getSampledTrajectoryIndices() const
+  {
+    return sampled_.indices;
+  }
+  /** [rows][T][O]: row 0 the optimal sequence, then the drawn rollouts, then the top N; the output AFTER each step */
+  const std::vector<float>& getSampledOutputTrajectories() const
+  {
+    return sampled_.outputs;
+  }
+  /** [rows][T + 1]: the cost of each step, the terminal cost last */
+  const std::vector<float>& getSampledCostTrajectories() const
+  {
+    return sampled_.costs;
+  }
+  /** [rows][T] */
+  const std::vector<int>& getSampledCrashStatusTrajectories() const
+  {
+    return sampled_.crash;
+  }
+  /** the top N trajectory costs, ascending, raw (the reference divides by the normaliser) */
+  const std::vector<float>& getTopNCosts() const
+  {
+    return sampled_.top_costs;
+  }
+  /** mppi_top_rollouts + mppi_replay_rollouts on the rows set above; rows other than the optimal sequence need a controller
+   *  constructed with save_samples */
+  void calculateSampledStateTrajectories(int system = 0)
+  {
+    check(sampled_.calculate(h_, num_timesteps_, output_dim_, system));
+  }
   std::vector<float> getSampledCostSeq() const
   {
     int kl = 0;
@@ -370,6 +421,7 @@ protected:
   int num_rollouts_, num_timesteps_;
   float dt_;
   int state_dim_ = 0, control_dim_ = 0, output_dim_ = 0, num_systems_ = 1;
+  SampledTrajectories sampled_;
 };
 
 /** reference: controllers/MPPI/mppi_controller.cuh */
@@ -377,9 +429,10 @@ class VanillaMPPIController : public Controller
 {
 public:
   VanillaMPPIController(const std::string& model, int num_rollouts, int num_timesteps, float dt, int max_iter, float lambda,
-                        float alpha, unsigned long long seed = 42, int device = 0, int sampler_kind = MPPI_SAMPLER_GAUSSIAN)
+                        float alpha, unsigned long long seed = 42, int device = 0, int sampler_kind = MPPI_SAMPLER_GAUSSIAN,
+                        bool save_samples = false)
     : Controller(model, MPPI_CONTROLLER_VANILLA, num_rollouts, num_timesteps, dt, max_iter, lambda, alpha, seed, device, 0, 1, nullptr,
-                 sampler_kind)
+                 sampler_kind, save_samples)
   {
   }
 };
@@ -390,9 +443,10 @@ class TubeMPPIController : public Controller
 {
 public:
   TubeMPPIController(const std::string& model, int num_rollouts, int num_timesteps, float dt, int max_iter, float lambda,
-                     float alpha, unsigned long long seed = 42, int device = 0, int sampler_kind = MPPI_SAMPLER_GAUSSIAN)
+                     float alpha, unsigned long long seed = 42, int device = 0, int sampler_kind = MPPI_SAMPLER_GAUSSIAN,
+                     bool save_samples = false)
     : Controller(model, MPPI_CONTROLLER_TUBE, num_rollouts, num_timesteps, dt, max_iter, lambda, alpha, seed, device, 0, 1, nullptr,
-                 sampler_kind)
+                 sampler_kind, save_samples)
   {
   }
   /** for a controller created with MPPI_SAMPLER_COLORED (any other: MPPI_ERR_STATE) */

@@ -315,6 +315,65 @@ public:
   {
     return getFreeEnergyStatistics().real_sys.normalizer;
   }
+  /* ---- what the sampled rollouts did (sampled_trajectories.hpp; reference: controller.cuh:229-296, 724-778) ---- */
+  /** the N lowest-cost rollouts of the last iteration join the replayed rows (N <= 256) */
+  void setTopNSampledControlTrajectories(int n)
+  {
+    sampled_.top_n = n;
+    requireSavedSamples();
+  }
+  /** int(fraction * K) rollouts drawn without replacement from the first 98 % join them */
+  void setPercentageSampledControlTrajectories(float fraction)
+  {
+    sampled_.fraction = fraction;
+    requireSavedSamples();
+  }
+  void setSampledTrajectoriesSeed(unsigned long long seed)
+  {
+    sampled_.seed = seed;
+  }
+  int getTotalSampledTrajectories() const
+  {
+    return (int)sampled_.indices.size();
+  }
+  const std::vector<int>& getSampledTrajectoryIndices() const
+  {
+    return sampled_.indices;
+  }
+  /** [rows][T][O]: row 0 the optimal sequence, then the drawn rollouts, then the top N; the output AFTER each step */
+  const std::vector<float>& getSampledOutputTrajectories() const
+  {
+    return sampled_.outputs;
+  }
+  /** [rows][T + 1]: the cost of each step, the terminal cost last */
+  const std::vector<float>& getSampledCostTrajectories() const
+  {
+    return sampled_.costs;
+  }
+  /** [rows][T] */
+  const std::vector<int>& getSampledCrashStatusTrajectories() const
+  {
+    return sampled_.crash;
+  }
+  /** the top N trajectory costs, ascending, raw (the reference divides by the normaliser) */
+  const std::vector<float>& getTopNCosts() const
+  {
+    return sampled_.top_costs;
+  }
+  /** the handle is created on first use: ask for sampled rollouts BEFORE the first computeControl, the handle then saves its
+   *  samples (cfg.save_samples) */
+  void requireSavedSamples()
+  {
+    if (h_ && !saved_samples_ && sampled_.wantsSamples())
+      throw Error(MPPI_ERR_STATE, "set the sampled control trajectories before the controller's first use: its handle was "
+                                  "created without save_samples");
+  }
+  /** mppi_top_rollouts + mppi_replay_rollouts on the rows set above */
+  void calculateSampledStateTrajectories(int system = 0)
+  {
+    ensureHandle();
+    check(sampled_.calculate(h_, params_.num_timesteps_, OUTPUT_DIM, system));
+  }
   std::vector<float> getSampledCostSeq() const
   {
     std::vector<float> c((size_t)(kind_ == MPPI_CONTROLLER_TUBE || kind_ == MPPI_CONTROLLER_ROBUST ? 2 : 1) * NUM_ROLLOUTS);
@@ -383,6 +442,8 @@ protected:
     cfg.seed = (unsigned long long)params_.seed_;
     cfg.noise_source = MPPI_NOISE_PHILOX_FUSED;
     cfg.stream = (void*)stream_;
+    cfg.save_samples = sampled_.wantsSamples() ? 1 : 0;
+    saved_samples_ = cfg.save_samples != 0;
     // dynamics_rollout_dim_ = (rollouts per block, lanes per rollout, .) is honoured or refused, never replaced: (0, 0, .) asks
     // for the engine's default, anything else has to be one of RolloutShapes<...>::type (the reference's (64, 4, 1) is)
     cfg.block_x = (int)params_.dynamics_rollout_dim_.x;
@@ -507,6 +568,8 @@ protected:
 
   PARAMS_T params_;
   mppi_handle h_ = nullptr;
+  SampledTrajectories sampled_;  ///< sampled_trajectories.hpp
+  bool saved_samples_ = false;   ///< the handle was created with cfg.save_samples
   int kind_;
   hipStream_t stream_;
   control_trajectory init_control_traj_;

@@ -16,6 +16,7 @@
 #include "rmppi_kernels.hpp"
 #include "linearize_kernel.hpp"
 #include "feedback_kernel.hpp"
+#include "replay_kernel.hpp"
 
 namespace mppi
 {
@@ -239,6 +240,14 @@ struct ModelBase
     err = "the model's Dynamics class declares no computeGrad";
     return MPPI_ERR_UNSUPPORTED;
   }
+  /** a.n rows (saved samples, or the current control sequence) run again through the model's plugins, their outputs, step costs and
+   *  crash flags kept: one launch of kernels::replayKernel on `stream` (engine/replay_kernel.hpp) in the lane form the model's
+   *  trajectory re-roll uses; `s`: the sampler state of the last rollout launch with the means the likelihood-ratio term reads */
+  virtual mppi_status launchReplay(const kernels::ReplayArgs& a, const SamplerLaunchState& s, hipStream_t stream, std::string& err)
+  {
+    err = "model has no replay kernel";
+    return MPPI_ERR_UNSUPPORTED;
+  }
 };
 
 /** fingerprint of the structures a model translation unit and libmppi_amd.so exchange (mppi_register_model refuses a
@@ -249,8 +258,8 @@ struct ModelBase
  *  6: FinalizeArgs::phases / carry block of the split hand-over (round 5); 7: undeclaredBarrierFreePlugins; 8: the transposed
  *  record copy (RolloutArgs) and supportsMergeControl / launchMergeControl (both round 6); 9: LaunchRecord,
  *  listReplicatedLaneShapes / supportsRMPPIPipeline (the launch and model introspection of mppi_amd.h); 10: costmapChannels;
- *  11: hasComputeGrad / launchLinearize; 12: launchDdpBackward, setFeedbackGains' gains_on_device. */
-#define MPPI_ENGINE_ABI_VERSION 12
+ *  11: hasComputeGrad / launchLinearize; 12: launchDdpBackward, setFeedbackGains' gains_on_device; 13: launchReplay. */
+#define MPPI_ENGINE_ABI_VERSION 13
 
 constexpr int engineAbiFingerprint()
 {
@@ -258,7 +267,7 @@ constexpr int engineAbiFingerprint()
          (int)(sizeof(ModelBase) + 131 * sizeof(kernels::RolloutArgs) + 131 * 131 * sizeof(kernels::FinalizeArgs) +
                7 * sizeof(kernels::RMPPIArgs) + 17 * sizeof(kernels::InitEvalArgs) + 31 * sizeof(SamplerLaunchState) +
                37 * sizeof(kernels::MergeControlArgs) + 41 * sizeof(kernels::LinearizeArgs) +
-               43 * sizeof(kernels::DdpBackwardArgs));
+               43 * sizeof(kernels::DdpBackwardArgs) + 47 * sizeof(kernels::ReplayArgs));
 }
 
 }  // namespace engine

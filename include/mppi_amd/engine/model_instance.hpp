@@ -1295,6 +1295,58 @@ struct ModelT : ModelBase
     }
     return ModelBase::launchDdpBackward(a, stream, err);
   }
+
+  /** one form of replayKernel: `rd` is the dynamics object it takes (the model, or one of its replicated-lane forms), BY the
+   *  contract lanes per row */
+  template <int BY, class RD_T>
+  mppi_status launchReplayForm(const char* what, RD_T& rd, const SAMPLING_T& rs, const kernels::ReplayArgs& a, hipStream_t stream,
+                               std::string& err)
+  {
+    const size_t smem = kernels::replaySharedBytes(rd, cost, BY);
+    if (smem > MAX_LDS_BYTES)
+      return ldsOverflow(what, smem, err);
+    constexpr int ROWS = BY == 1 ? kernels::replayBlockRows<RD_T>() : 1;
+    return launchChecked(what, kernels::replayKernel<RD_T, COST_T, SAMPLING_T, BY>, dim3((a.n + ROWS - 1) / ROWS),
+                         dim3(BY == 1 ? 64 : 1, BY, 1), smem, stream, err, rd, cost, rs, a);
+  }
+  /** the form is chosen as launchFinalize chooses the re-roll's: the one-rollout-per-wave form of an NN model, else its
+   *  replicated-lane form, else the model itself with FIN_BY lanes */
+  mppi_status launchReplay(const kernels::ReplayArgs& a, const SamplerLaunchState& s, hipStream_t stream, std::string& err) override
+  {
+    if (!blobsReady(err))
+      return MPPI_ERR_STATE;
+    if (a.n < 1 || !a.x0_d || !a.optimal_d || !a.idx_d || !a.y_d || !a.cost_d || !a.crash_d)
+    {
+      err = "replayKernel: n >= 1 rows and six device pointers";
+      return MPPI_ERR_INVALID_ARG;
+    }
+    // the sampler as the last rollout launch saw it, on a copy: the model's own keeps what that launch left in it
+    const SAMPLING_T keep = smp;
+    prepSampler(s);
+    const SAMPLING_T rs = smp;
+    smp = keep;
+    if constexpr (has_finalize_form<DYN_FAST_T>::value)
+    {
+      const char* form = getenv("MPPI_AMD_FINALIZE_FORM");
+      if (!(form && form[0] == 'r'))
+      {
+        using WAVE_T = typename DYN_FAST_T::FINALIZE_FORM;
+        WAVE_T wave_form(dyn);
+        if (kernels::replaySharedBytes(wave_form, cost, 1) <= MAX_LDS_BYTES)
+          return launchReplayForm<1>("replayKernel (wave form)", wave_form, rs, a, stream, err);
+      }
+    }
+    if constexpr (!std::is_void<DYN_FAST_T>::value)
+    {
+      DYN_FAST_T fast(dyn);
+      bool usable = kernels::replaySharedBytes(fast, cost, 1) <= MAX_LDS_BYTES;
+      if constexpr (has_register_form<DYN_T>::value)
+        usable = usable && dyn.register_form_;
+      if (usable)
+        return launchReplayForm<1>("replayKernel (replicated lanes)", fast, rs, a, stream, err);
+    }
+    return launchReplayForm<FIN_BY>("replayKernel", dyn, rs, a, stream, err);
+  }
 };
 
 }  // namespace engine

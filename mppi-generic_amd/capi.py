@@ -150,6 +150,8 @@ SIGNATURES = {
     "mppi_get_costs": (C.c_int, [H, _f32p]),
     "mppi_get_stats": (C.c_int, [H, C.POINTER(MppiStats)]),
     "mppi_get_sampled_controls": (C.c_int, [H, _f32p]),
+    "mppi_top_rollouts": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mppi_replay_rollouts": (C.c_int, [H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mppi_get_optimal_control": (C.c_int, [H, _f32p]),
     "mppi_optimize": (C.c_int, [H, C.c_int, C.c_int]),
     "mppi_upload_state": (C.c_int, [H, _f32p]),

@@ -400,6 +400,22 @@ def lstm_blob_from_npz_dict(d, prefix=""):
     return np.concatenate(parts).astype(np.float32), fnn_blob_from_npz_dict(d, prefix + "output/dynamics_")
 
 
+def sampled_trajectory_list(num_rollouts, fraction=0.0, seed=None):
+    """the random part of the reference's sampled-trajectory list (controllers/controller.cu:63-84) as local rollout indices:
+    -1 (slot 0, the optimal sequence), then int(fraction * K) indices drawn without replacement from the first 98 % of the
+    rollouts — 0, 1, 2, ... when fraction > 0.98, as there — with numpy's default generator seeded with `seed`"""
+    k = int(num_rollouts)
+    m = min(int(fraction * k), k) if fraction > 0 else 0
+    if m <= 0:
+        drawn = np.empty(0, np.int32)
+    elif fraction > 0.98:
+        drawn = np.arange(m, dtype=np.int32)
+    else:
+        pool = int(k * 0.98)
+        drawn = np.random.default_rng(seed).choice(pool, size=min(m, pool), replace=False).astype(np.int32)
+    return np.concatenate([np.array([-1], np.int32), drawn])
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -711,6 +727,41 @@ class MPPIController:
         v = np.empty((self.num_systems, self.num_rollouts_local, self.num_timesteps, self.CONTROL_DIM), np.float32)
         self._check(self._lib.mppi_get_sampled_controls(self._h, v))
         return v
+
+    def top_rollouts(self, n, system=0):
+        """(indices, costs) of the n lowest-cost local rollouts of the last iteration, selected on the device
+        (mppi_top_rollouts): ascending cost, ties to the lower index, NaN last; costs as getSampledCostSeq gives them"""
+        n = int(n)
+        idx = np.empty(max(n, 0), np.int32)
+        cost = np.empty(max(n, 0), np.float32)
+        self._check(self._lib.mppi_top_rollouts(self._h, int(system), n, idx.ctypes.data, cost.ctypes.data))
+        return idx, cost
+
+    def replay_rollouts(self, indices, system=0):
+        """the rows `indices` (local rollout indices of the saved samples; -1: the current control sequence) run again on the
+        device (mppi_replay_rollouts): (outputs (n, T, O) after each step, step costs (n, T + 1) with the terminal cost last,
+        crash flags (n, T))"""
+        idx = np.ascontiguousarray(np.asarray(indices).reshape(-1), np.int32)
+        n, T = idx.size, self.num_timesteps
+        y = np.empty((n, T, self.OUTPUT_DIM), np.float32)
+        cost = np.empty((n, T + 1), np.float32)
+        crash = np.empty((n, T), np.int32)
+        self._check(self._lib.mppi_replay_rollouts(self._h, int(system), idx.ctypes.data, n, y.ctypes.data, cost.ctypes.data,
+                                                   crash.ctypes.data))
+        return y, cost, crash
+
+    def sampled_trajectories(self, top_n=0, fraction=0.0, seed=None, system=0):
+        """the reference's calculateSampledStateTrajectories (controllers/controller.cu:55-179): replays slot 0 = the optimal
+        sequence, then int(fraction * K) rollouts drawn without replacement from the first 98 % of the local rollouts (the last
+        ones are pure noise) with a seeded host generator, then the top_n lowest-cost rollouts.  Returns a dict: "indices" (the
+        list, -1 first), "outputs", "costs", "crash" (replay_rollouts of it) and "top_costs" (top_n costs, ascending)."""
+        idx = sampled_trajectory_list(self.num_rollouts_local, fraction, seed)
+        top_costs = np.empty(0, np.float32)
+        if top_n > 0:
+            top_idx, top_costs = self.top_rollouts(top_n, system)
+            idx = np.concatenate([idx, top_idx])
+        y, cost, crash = self.replay_rollouts(idx, system)
+        return {"indices": idx, "outputs": y, "costs": cost, "crash": crash, "top_costs": top_costs}
 
     def getStats(self):
         st = MppiStats()

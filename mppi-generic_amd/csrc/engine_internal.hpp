@@ -230,6 +230,10 @@ struct mppi_handle_s
   bool have_result = false;        // a mppi_compute_control has succeeded: the out block / outbox holds its sequences
   HipBuffer<float> lin_in_d;       // mppi_linearize: the caller's points [n][S] | [n][C]
   HipBuffer<float> lin_out_d;      // mppi_linearize / mppi_linearize_trajectory: A [n][S][S] | B [n][S][C]
+  /* mppi_top_rollouts / mppi_replay_rollouts (engine_replay.hip): empty until the first call, grown on demand */
+  HipBuffer<float> top_d;          // [n] indices | [n] costs of the last selection (256 + 256 words)
+  HipBuffer<float> replay_d;       // y [n][T][O] | step costs [n][T + 1] | crash flags [n][T] | the index list [n]
+  std::vector<float> replay_h;     // the results on their way to the caller's arrays
   /* mppi_set_feedback_params / mppi_compute_feedback[_at] (engine/feedback_kernel.hpp) */
   std::vector<float> fb_params_h;  // Q [S][S] | R [C][C] | Qf [S][S]; empty: never set (identities on first use)
   bool fb_params_dirty = false;    // fb_params_h is newer than fb_params_d

@@ -15,7 +15,9 @@ K = 16384, T = 150 — the vanilla iteration on the default MFMA shape, fused an
 the same run, as the yardstick; registration unit examples/autorally_robust_model/autorally_robust_model.hip, or an argument ending
 in .so)
 linearize / feedback: wall clock of mppi_linearize_trajectory / mppi_compute_feedback on Cartpole T = 100 and AutoRally-NN T = 150;
-not part of the default set.)"""
+not part of the default set.
+replay: wall clock of mppi_top_rollouts(32) and mppi_replay_rollouts(33 rows) next to mppi_linearize_trajectory on Cartpole
+K = 16384, T = 100; not part of the default set.)"""
 import os
 import sys
 
@@ -206,3 +208,32 @@ if "feedback" in which:
         print("%-10s K=%d T=%d linearize_trajectory %.1f us (p10 %.1f, p90 %.1f); compute_feedback %.1f us (p10 %.1f, p90 %.1f)"
               % ((name, cfg["K"], cfg["T"]) + tuple(lin) + tuple(fb)), flush=True)
         eng.close()
+if "replay" in which:
+    # mppi_top_rollouts(n = 32) and mppi_replay_rollouts(n = 33: the optimal sequence and the 32 best rollouts) next to
+    # mppi_linearize_trajectory on the same handle (Cartpole K = 16384, T = 100, saved samples): wall time of the whole call (launch,
+    # copies, one synchronisation), median and p10 / p90 over 5000 calls after warm-up, as the linearize mode above.  The kernels'
+    # own times are not in these figures; take them from a kernel trace of this mode, in a run of its own.
+    import time  # noqa: E402
+    cfg = cartpole_cfg(K=16384, T=100)
+    eng = make_engine(cfg, save_samples=True)
+    for _ in range(200):
+        eng.computeControl(cfg["x0"], 1)
+        eng.computeGradTrajectory()
+        rows = np.concatenate([np.array([-1], np.int32), eng.top_rollouts(32)[0]])
+        eng.replay_rollouts(rows)
+
+    def timed(fn, n=5000):
+        t = []
+        for _ in range(n):
+            t0 = time.perf_counter()
+            fn()
+            t.append((time.perf_counter() - t0) * 1e6)
+        return np.percentile(t, [50, 10, 90])
+
+    eng.getTargetStateSeq()
+    lin = timed(eng.computeGradTrajectory)
+    top = timed(lambda: eng.top_rollouts(32))
+    rep = timed(lambda: eng.replay_rollouts(rows))
+    print("cartpole   K=%d T=%d linearize_trajectory %.1f us (p10 %.1f, p90 %.1f); top_rollouts(32) %.1f us (p10 %.1f, p90 %.1f); "
+          "replay_rollouts(33) %.1f us (p10 %.1f, p90 %.1f)" % ((cfg["K"], cfg["T"]) + tuple(lin) + tuple(top) + tuple(rep)), flush=True)
+    eng.close()
