@@ -274,6 +274,16 @@ static inline mppi_status takeControls(mppi_handle h, AfterWait after_wait)
   return MPPI_OK;
 }
 
+/** Nothing has weight: every trajectory cost of system z was +inf (or NaN) in the last merge — the baseline is not finite, or the
+ *  normaliser is not a positive finite number — and u* is NaN.  The Vanilla control phase clamps u* to the control ranges with
+ *  fminf(fmaxf(lo, u), hi) (the reference's enforceConstraints), which DROPS a NaN: with the default ranges the control handed
+ *  back is -FLT_MAX in every entry and passes a finiteness check.  Read from the statistics that travel with the control. */
+static inline bool nothingHasWeight(mppi_handle h, int z)
+{
+  const mppi_system_stats* s = h->sys.stats[z];
+  return !std::isfinite(s->baseline) || !std::isfinite(s->normalizer) || !(s->normalizer > 0.0f);
+}
+
 /** reference: controllers/MPPI/mppi_controller.cu:152-231; ColoredMPPI/colored_mppi_controller.cu:150-237 */
 static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, int stride)
 {
@@ -388,6 +398,8 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
     stamp(6);
     if (!allFinite(h->control_h))
       return fail(h, MPPI_ERR_NAN, "mppi_compute_control: non-finite value in the control sequence");
+    if (h->cfg.num_iters >= 1 && nothingHasWeight(h, 0))
+      return fail(h, MPPI_ERR_NAN, "mppi_compute_control: no rollout has weight (every trajectory cost is non-finite)");
     return MPPI_OK;
   }
   // one hand-over in (x0, nominal control, control history), one back (control, state and output trajectories, stats):
@@ -413,6 +425,8 @@ static mppi_status computeControlVanilla(mppi_handle h, const float* x0_true, in
   // base_plant.hpp:515-528 checks both the control and the state trajectory
   if (!allFinite(h->control_h) || !allFinite(h->state_h))
     return fail(h, MPPI_ERR_NAN, "mppi_compute_control: non-finite value in the control or state sequence");
+  if (h->cfg.num_iters >= 1 && nothingHasWeight(h, 0))
+    return fail(h, MPPI_ERR_NAN, "mppi_compute_control: no rollout has weight (every trajectory cost is non-finite)");
   return MPPI_OK;
 }
 
