@@ -513,7 +513,7 @@ public:
    *  most of the spilled-SGPR reads of the step loop and are SLOWER here (profiles/r06_step_source_ab.json) — A/B:
    *  -DMPPI_STEP_SOURCE_QUAD=1|2 */
   static constexpr int MPPI_STEP_SOURCE = MPPI_STEP_SOURCE_QUAD;
-  /** the form the role-pipelined ROBUST rollout kernel runs instead (engine/model_instance.hpp: withRmppiPipelineDynamics) */
+  /** the form the role-pipelined ROBUST rollout kernel runs instead (engine/model_instance.hpp: RMPPI_PIPE_T) */
   using RMPPI_PIPELINE_FORM = RacerDubinsElevationLSTMUncertaintyQuadRobust;
   RacerDubinsElevationLSTMUncertaintyQuad(const RacerDubinsElevationLSTMUncertainty& other)
     : RacerDubinsElevationLSTMUncertaintyQuadImpl<RacerDubinsElevationLSTMUncertaintyQuad>(other)

@@ -157,73 +157,15 @@ struct ModelT : ModelBase
     }
     return ModelBase::setFeedbackGains(gains, T, accumulate_all_states, gains_on_device, stream, err);
   }
-  /** Robust MPPI's two kernels run on the replicated-lane (FAST) form of a model when there is one — and when it is usable:
-   *  the four-lane forms of the RACER models are compiled for the reference's network shapes, a network of another shape
-   *  (`register_form_` false) runs the kernels on the model itself, one lane per rollout and system (round 3; it used to be
-   *  refused).  f(rm_dyn) is called with the object the kernels take. */
-  static constexpr bool RMPPI_HAS_FALLBACK = has_register_form<DYN_T>::value && !std::is_void<DYN_FAST_T>::value;
-  bool rmppiUseFast() const
-  {
-    if constexpr (std::is_void<DYN_FAST_T>::value)
-      return false;
-    else if constexpr (has_register_form<DYN_T>::value)
-      return dyn.register_form_;
-    else
-      return true;
-  }
-  template <class F>
-  auto withRmppiDynamics(F&& f)
-  {
-    if constexpr (std::is_void<DYN_FAST_T>::value)
-      return f(dyn);
-    else if constexpr (RMPPI_HAS_FALLBACK)
-    {
-      if (!dyn.register_form_)
-        return f(dyn);
-      DYN_FAST_T fast(dyn);
-      return f(fast);
-    }
-    else
-    {
-      DYN_FAST_T fast(dyn);
-      return f(fast);
-    }
-  }
-  size_t rmppiSharedBytes(int bx, int T) override
-  {
-    if constexpr (RMPPI)
-    {
-      smp.params_.num_timesteps = T;
-      smp.params_.num_distributions = 2;
-      return withRmppiDynamics([&](auto& rm_dyn) { return kernels::rmppiSharedBytes(rm_dyn, cost, fb, smp, bx); });
-    }
-    return 0;
-  }
-  /** the role-pipelined Robust MPPI kernels (rmppi_pipeline_kernel.hpp) exist for models with a replicated-lane form, and for
-   *  models registered for the role-pipelined rollout (PIPELINE: one lane per rollout, no block barrier inside the per-step
-   *  methods) — with a sampler whose rows may live in HBM and need no block-wide prologue of their own (the Gaussian one) */
-  static constexpr bool rmppiHasPipeline()
-  {
-    if constexpr (!RMPPI || !SAMPLING_T::SUPPORTS_GLOBAL_ROWS || SAMPLING_T::COLORED)
-      return false;
-    else if constexpr (!std::is_void<DYN_FAST_T>::value)
-      return kernels::replicated_lanes<DYN_FAST_T>::value > 1;
-    else
-      return PIPELINE;
-  }
-  /** can the pipelined kernels run with the networks loaded right now (replicated-lane forms exist for one shape only) */
-  bool rmppiPipelineUsable() const
-  {
-    if constexpr (!rmppiHasPipeline())
-      return false;
-    else if constexpr (std::is_void<DYN_FAST_T>::value)
-      return true;
-    else
-      return rmppiUseFast();
-  }
-  /** f(pipe_dyn): the dynamics object the pipelined kernels take — the replicated-lane form (or the form IT names for this
-   *  kernel: `using RMPPI_PIPELINE_FORM = ...` — a class of the same arithmetic whose trade-offs are made for a block of 11-15
-   *  waves at 128-168 VGPRs each: dynamics/racer_dubins/racer_dubins_elevation_lstm_unc.hpp), or the model itself */
+  /* ---- the forms of a model: the object a kernel takes.  The model itself (`dyn`); its replicated-lane form REP_T(dyn) (MFMA /
+   *  four-lane dynamics); the form that class may name for ONE rollout on a wave, REP_T::FINALIZE_FORM(dyn) (NN models: lane =
+   *  neuron, utils/nn_helpers/fnn_wave.hpp); and the form it may name for the role-pipelined Robust kernels, RMPPI_PIPE_T(dyn)
+   *  (`using RMPPI_PIPELINE_FORM = ...` — a class of the same arithmetic whose trade-offs are made for a block of 11-15 waves at
+   *  128-168 VGPRs each: dynamics/racer_dubins/racer_dubins_elevation_lstm_unc.hpp).  A form is built from `dyn` at the launch, so
+   *  parameters, control ranges and blobs are shared. ---- */
+  using REP_T = DYN_FAST_T;
+  static constexpr bool HAS_REP = !std::is_void<REP_T>::value;
+  static constexpr bool HAS_WAVE = has_finalize_form<REP_T>::value;
   template <class T, class = void>
   struct rmppi_pipeline_form
   {
@@ -234,16 +176,128 @@ struct ModelT : ModelBase
   {
     using type = typename T::RMPPI_PIPELINE_FORM;
   };
-  template <class F>
-  auto withRmppiPipelineDynamics(F&& f)
+  using RMPPI_PIPE_T = std::conditional_t<HAS_REP, typename rmppi_pipeline_form<REP_T>::type, DYN_T>;
+  /** the four-lane forms of the RACER models are compiled for the reference's network shapes: a model that says which networks it
+   *  holds (`register_form_`) has a replicated-lane form for some of them only, every other one for whatever is loaded */
+  static constexpr bool REP_ALWAYS = HAS_REP && !has_register_form<DYN_T>::value;
+  /** can the replicated-lane form take the networks loaded now */
+  bool repUsable() const
   {
-    if constexpr (std::is_void<DYN_FAST_T>::value)
+    if constexpr (HAS_REP && !REP_ALWAYS)
+      return dyn.register_form_;
+    else
+      return HAS_REP;
+  }
+  /** f(form): FORM_T built from the model, or the model itself */
+  template <class FORM_T, class F>
+  auto withForm(F&& f)
+  {
+    if constexpr (std::is_same<FORM_T, DYN_T>::value)
       return f(dyn);
     else
     {
-      typename rmppi_pipeline_form<DYN_FAST_T>::type fast(dyn);
-      return f(fast);
+      FORM_T form(dyn);
+      return f(form);
     }
+  }
+  /** Robust MPPI's fused kernels run on the replicated-lane form of a model when it is usable, else on the model itself, one lane
+   *  per rollout and system (round 3; a network of another shape used to be refused).  f(rm_dyn): the object the kernels take. */
+  template <class F>
+  auto withRmppiDynamics(F&& f)
+  {
+    if constexpr (!REP_ALWAYS)
+    {
+      if (!repUsable())
+        return f(dyn);
+    }
+    return withForm<std::conditional_t<HAS_REP, REP_T, DYN_T>>(f);
+  }
+
+  /** this launch draws its noise inside the step loop: the sampler can, and no noise was injected */
+  bool drawsInLoop() const
+  {
+    return SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
+  }
+  /** the instantiation of a kernel template this launch takes, over DRAW_IN_LOOP x ROWS_HBM: k(draw, hbm) names one, the two given
+   *  as std::bool_constant values.  HBM_FORMS: the template has forms for the sample rows in HBM (long horizons) — instantiated for
+   *  samplers that support them only; DRAW: this block shape can draw in the loop. */
+  template <bool HBM_FORMS, bool DRAW = SAMPLING_T::IN_LOOP_DRAW, class K>
+  auto kernelVariant(K k) const
+  {
+    constexpr std::bool_constant<DRAW> draw{};
+    constexpr std::false_type no{};
+    const bool in_loop = DRAW && drawsInLoop();
+    auto kfn = in_loop ? k(draw, no) : k(no, no);
+    if constexpr (HBM_FORMS && SAMPLING_T::SUPPORTS_GLOBAL_ROWS)
+    {
+      if (smp.rows_global_d_)
+        kfn = in_loop ? k(draw, std::true_type{}) : k(no, std::true_type{});
+    }
+    return kfn;
+  }
+  /** the one writer of last_launch: a rollout launch that went out leaves what it ran */
+  mppi_status noted(mppi_status st, int family, int bx, int by, int bz, bool streamed_merge)
+  {
+    if (st == MPPI_OK)
+      last_launch = LaunchRecord{family, bx, by, bz, smp.rows_global_d_ != nullptr, streamed_merge};
+    return st;
+  }
+
+  /* ---- Robust MPPI: one function per launch family gives its block (LDS bytes, threads, rings); the LDS queries and the
+   *  launches both read it ---- */
+  template <class RM_DYN_T>
+  BlockPlan<> rmppiPlan(const RM_DYN_T& rm_dyn, int bx) const
+  {
+    return {kernels::rmppiSharedBytes(rm_dyn, cost, fb, smp, bx), dim3(bx * kernels::replicated_lanes<RM_DYN_T>::value, 1, 2), bx, 0};
+  }
+  /** smem 0: not even the shortest rings fit next to the sample rows */
+  template <class PD_T>
+  BlockPlan<kernels::RMPPIPipeRings> rmppiPipelinePlan(const PD_T& pd) const
+  {
+    const kernels::RMPPIPipeRings r = kernels::rmppiPipelineRings(pd, cost, fb, smp, MAX_LDS_BYTES);
+    return {r.out_steps ? kernels::rmppiPipelineSharedBytes(pd, cost, fb, smp, r) : 0,
+            dim3(64 * kernels::rmppiPipelineWaves<PD_T>(), 1, 1), 64, r};
+  }
+  template <class RM_DYN_T>
+  BlockPlan<> initEvalPlan(const RM_DYN_T& rm_dyn) const
+  {
+    return {kernels::initEvalSharedBytes<RM_DYN_T, COST_T, SAMPLING_T>(rm_dyn, cost, 64),
+            dim3(64 * kernels::replicated_lanes<RM_DYN_T>::value, 1, 1), 64, 0};
+  }
+  /** ring 0: the rows of 64 rollouts and a ring do not fit the LDS */
+  template <class PD_T>
+  BlockPlan<> initEvalPipelinePlan(const PD_T& pd, int T) const
+  {
+    const int ring = kernels::initEvalPipelineRing(pd, cost, T, MAX_LDS_BYTES);
+    constexpr int WAVES = kernels::replicated_lanes<PD_T>::value + kernels::INIT_EVAL_PIPE_SAMPLERS + kernels::INIT_EVAL_PIPE_COSTS;
+    return {ring ? kernels::initEvalPipelineSharedBytes(pd, cost, T, ring) : 0, dim3(64 * WAVES, 1, 1), 64, ring};
+  }
+  size_t rmppiSharedBytes(int bx, int T) override
+  {
+    if constexpr (RMPPI)
+    {
+      smp.params_.num_timesteps = T;
+      smp.params_.num_distributions = 2;
+      return withRmppiDynamics([&](auto& rm_dyn) { return rmppiPlan(rm_dyn, bx).smem; });
+    }
+    return 0;
+  }
+  /** the role-pipelined Robust MPPI kernels (rmppi_pipeline_kernel.hpp) exist for models with a replicated-lane form, and for
+   *  models registered for the role-pipelined rollout (PIPELINE: one lane per rollout, no block barrier inside the per-step
+   *  methods) — with a sampler whose rows may live in HBM and need no block-wide prologue of their own (the Gaussian one) */
+  static constexpr bool rmppiHasPipeline()
+  {
+    if constexpr (!RMPPI || !SAMPLING_T::SUPPORTS_GLOBAL_ROWS || SAMPLING_T::COLORED)
+      return false;
+    else if constexpr (HAS_REP)
+      return kernels::replicated_lanes<REP_T>::value > 1;
+    else
+      return PIPELINE;
+  }
+  /** can the pipelined kernels run with the networks loaded right now (replicated-lane forms exist for one shape only) */
+  bool rmppiPipelineUsable() const
+  {
+    return rmppiHasPipeline() && (!HAS_REP || repUsable());
   }
   size_t rmppiPipelineSharedBytes(int T) override
   {
@@ -253,10 +307,7 @@ struct ModelT : ModelBase
         return 0;
       smp.params_.num_timesteps = T;
       smp.params_.num_distributions = 2;
-      return withRmppiPipelineDynamics([&](auto& pd) -> size_t {
-        const kernels::RMPPIPipeRings r = kernels::rmppiPipelineRings(pd, cost, fb, smp, MAX_LDS_BYTES);
-        return r.out_steps ? kernels::rmppiPipelineSharedBytes(pd, cost, fb, smp, r) : 0;
-      });
+      return withForm<RMPPI_PIPE_T>([&](auto& pd) { return rmppiPipelinePlan(pd).smem; });
     }
     return 0;
   }
@@ -264,24 +315,20 @@ struct ModelT : ModelBase
   {
     if constexpr (rmppiHasPipeline())
     {
-      return withRmppiPipelineDynamics([&](auto& pd) -> mppi_status {
+      return withForm<RMPPI_PIPE_T>([&](auto& pd) -> mppi_status {
         using PD_T = std::decay_t<decltype(pd)>;
-        const kernels::RMPPIPipeRings r = kernels::rmppiPipelineRings(pd, cost, fb, smp, MAX_LDS_BYTES);
-        if (r.out_steps == 0)
-        {
-          err = "pipelined RMPPI rollout kernel: the rings do not fit 160 KiB of LDS next to the sample rows";
-          return MPPI_ERR_LDS_OVERFLOW;
-        }
-        const size_t smem = kernels::rmppiPipelineSharedBytes(pd, cost, fb, smp, r);
-        const bool in_loop = SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
-        auto kfn = in_loop ? kernels::rolloutRMPPIPipelineKernel<PD_T, COST_T, DeviceDDP<DYN_T>, SAMPLING_T, SAMPLING_T::IN_LOOP_DRAW>
-                           : kernels::rolloutRMPPIPipelineKernel<PD_T, COST_T, DeviceDDP<DYN_T>, SAMPLING_T, false>;
-        return launchChecked("rolloutRMPPIPipelineKernel", kfn, dim3((a.base.num_rollouts + 63) / 64),
-                             dim3(64 * kernels::rmppiPipelineWaves<PD_T>(), 1, 1), smem, stream, err, pd, cost, fb, smp, a, r);
+        const auto p = rmppiPipelinePlan(pd);
+        if (p.ring.out_steps == 0)
+          return refuse(MPPI_ERR_LDS_OVERFLOW,
+                        "pipelined RMPPI rollout kernel: the rings do not fit 160 KiB of LDS next to the sample rows", err);
+        auto kfn = kernelVariant<false>([](auto draw, auto) {
+          return kernels::rolloutRMPPIPipelineKernel<PD_T, COST_T, DeviceDDP<DYN_T>, SAMPLING_T, decltype(draw)::value>;
+        });
+        return launchChecked("rolloutRMPPIPipelineKernel", kfn, p.grid(a.base.num_rollouts), p.block, p.smem, stream, err, pd, cost,
+                             fb, smp, a, p.ring);
       });
     }
-    err = "model has no role-pipelined Robust MPPI kernel";
-    return MPPI_ERR_LAUNCH_SHAPE;
+    return refuse(MPPI_ERR_LAUNCH_SHAPE, "model has no role-pipelined Robust MPPI kernel", err);
   }
   mppi_status launchInitEval(bool pipeline, const kernels::InitEvalArgs& a, const SamplerLaunchState& s, hipStream_t stream,
                              std::string& err) override
@@ -291,7 +338,6 @@ struct ModelT : ModelBase
       if (!blobsReady(err))
         return MPPI_ERR_STATE;
       prepSampler(s);
-      constexpr int BX = 64;
       if constexpr (rmppiHasPipeline())
       {
         // the candidate rollouts as blocks of role waves (rmppi_pipeline_kernel.hpp) when the rows of 64 rollouts and a ring
@@ -299,31 +345,22 @@ struct ModelT : ModelBase
         if (pipeline && rmppiPipelineUsable())
         {
           bool launched = false;
-          const mppi_status st = withRmppiPipelineDynamics([&](auto& pd) -> mppi_status {
-            using PD_T = std::decay_t<decltype(pd)>;
-            const int ring = kernels::initEvalPipelineRing(pd, cost, a.num_timesteps, MAX_LDS_BYTES);
-            if (ring == 0)
-              return MPPI_OK;  // rows + ring do not fit: the fused kernel below
+          const mppi_status st = withForm<RMPPI_PIPE_T>([&](auto& pd) -> mppi_status {
+            const BlockPlan<> p = initEvalPipelinePlan(pd, a.num_timesteps);
+            if (p.ring == 0)
+              return MPPI_OK;
             launched = true;
-            constexpr int REP = kernels::replicated_lanes<PD_T>::value;
-            const size_t smem = kernels::initEvalPipelineSharedBytes(pd, cost, a.num_timesteps, ring);
-            auto kfn = kernels::initEvalPipelineKernel<PD_T, COST_T, SAMPLING_T>;
-            constexpr int WAVES = REP + kernels::INIT_EVAL_PIPE_SAMPLERS + kernels::INIT_EVAL_PIPE_COSTS;
-            return launchChecked("initEvalPipelineKernel", kfn, dim3((a.num_eval_rollouts + BX - 1) / BX), dim3(64 * WAVES, 1, 1), smem,
-                                 stream, err, pd, cost, smp, a, ring);
+            return launchChecked("initEvalPipelineKernel", kernels::initEvalPipelineKernel<std::decay_t<decltype(pd)>, COST_T, SAMPLING_T>,
+                                 p.grid(a.num_eval_rollouts), p.block, p.smem, stream, err, pd, cost, smp, a, p.ring);
           });
           if (launched || st != MPPI_OK)
             return st;
         }
       }
-      // models with replicated-lane (MFMA / four-lane) dynamics run both Robust MPPI kernels on them (withRmppiDynamics)
       return withRmppiDynamics([&](auto& rm_dyn) -> mppi_status {
-        using RM_DYN_T = std::decay_t<decltype(rm_dyn)>;
-        constexpr int REP = kernels::replicated_lanes<RM_DYN_T>::value;
-        const size_t smem = kernels::initEvalSharedBytes<RM_DYN_T, COST_T, SAMPLING_T>(rm_dyn, cost, BX);
-        auto kfn = kernels::initEvalKernel<RM_DYN_T, COST_T, SAMPLING_T, BX>;
-        return launchChecked("initEvalKernel", kfn, dim3((a.num_eval_rollouts + BX - 1) / BX), dim3(BX * REP, 1, 1), smem, stream,
-                             err, rm_dyn, cost, smp, a);
+        const BlockPlan<> p = initEvalPlan(rm_dyn);
+        return launchChecked("initEvalKernel", kernels::initEvalKernel<std::decay_t<decltype(rm_dyn)>, COST_T, SAMPLING_T, 64>,
+                             p.grid(a.num_eval_rollouts), p.block, p.smem, stream, err, rm_dyn, cost, smp, a);
       });
     }
     return ModelBase::launchInitEval(pipeline, a, s, stream, err);
@@ -335,19 +372,25 @@ struct ModelT : ModelBase
     {
       return withRmppiDynamics([&](auto& rm_dyn) -> mppi_status {
         using RM_DYN_T = std::decay_t<decltype(rm_dyn)>;
-        constexpr int REP = kernels::replicated_lanes<RM_DYN_T>::value;
-        const size_t smem = kernels::rmppiSharedBytes(rm_dyn, cost, fb, smp, BX);
-        if (smem > MAX_LDS_BYTES)
-          return ldsOverflow("RMPPI rollout kernel", smem, err);
-        const bool in_loop = SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
-        auto kfn = in_loop ? kernels::rolloutRMPPIKernel<RM_DYN_T, COST_T, DeviceDDP<DYN_T>, SAMPLING_T, BX, SAMPLING_T::IN_LOOP_DRAW>
-                           : kernels::rolloutRMPPIKernel<RM_DYN_T, COST_T, DeviceDDP<DYN_T>, SAMPLING_T, BX, false>;
-        return launchChecked("rolloutRMPPIKernel", kfn, dim3((a.base.num_rollouts + BX - 1) / BX), dim3(BX * REP, 1, 2), smem, stream,
-                             err, rm_dyn, cost, fb, smp, a);
+        const BlockPlan<> p = rmppiPlan(rm_dyn, BX);
+        if (p.smem > MAX_LDS_BYTES)
+          return ldsOverflow("RMPPI rollout kernel", p.smem, err);
+        auto kfn = kernelVariant<false>([](auto draw, auto) {
+          return kernels::rolloutRMPPIKernel<RM_DYN_T, COST_T, DeviceDDP<DYN_T>, SAMPLING_T, BX, decltype(draw)::value>;
+        });
+        return launchChecked("rolloutRMPPIKernel", kfn, p.grid(a.base.num_rollouts), p.block, p.smem, stream, err, rm_dyn, cost, fb,
+                             smp, a);
       });
     }
-    err = "model is not registered for Robust MPPI";
-    return MPPI_ERR_UNSUPPORTED;
+    return refuse(MPPI_ERR_UNSUPPORTED, "model is not registered for Robust MPPI", err);
+  }
+  /** the family of a Robust rollout launch, in order of precedence; MPPI_FAMILY_NONE: no kernel for such a block.  32 rollouts: for
+   *  horizons whose sample rows for 64 rollouts x 2 systems do not fit the LDS */
+  int rmppiFamily(int bx, bool pipeline) const
+  {
+    if (pipeline && bx == 64 && rmppiPipelineUsable())
+      return MPPI_FAMILY_RMPPI_PIPELINE;
+    return bx == 64 || bx == 32 ? MPPI_FAMILY_RMPPI : MPPI_FAMILY_NONE;
   }
   mppi_status launchRMPPI(int bx, bool pipeline, const kernels::RMPPIArgs& a, const SamplerLaunchState& s, hipStream_t stream,
                           std::string& err) override
@@ -357,27 +400,16 @@ struct ModelT : ModelBase
       if (!blobsReady(err))
         return MPPI_ERR_STATE;
       if (!fb.fb_gain_traj_d_ || fb.num_timesteps_ != s.num_timesteps)
-      {
-        err = "Robust MPPI needs the DDP feedback gains [T][S][C] (mppi_set_feedback_gains) before it can run";
-        return MPPI_ERR_STATE;
-      }
+        return refuse(MPPI_ERR_STATE,
+                      "Robust MPPI needs the DDP feedback gains [T][S][C] (mppi_set_feedback_gains) before it can run", err);
       prepSampler(s);
-      auto noted = [&](int family, mppi_status st) {
-        if (st == MPPI_OK)
-          last_launch = LaunchRecord{family, bx, 1, 2, smp.rows_global_d_ != nullptr, false};
-        return st;
-      };
-      if constexpr (rmppiHasPipeline())
-      {
-        if (pipeline && bx == 64 && rmppiPipelineUsable())
-          return noted(MPPI_FAMILY_RMPPI_PIPELINE, launchRMPPIPipeline(a, stream, err));
-      }
-      if (bx == 64)
-        return noted(MPPI_FAMILY_RMPPI, launchRMPPIShape<64>(a, stream, err));
-      if (bx == 32)  // horizons whose sample rows for 64 rollouts x 2 systems do not fit the LDS
-        return noted(MPPI_FAMILY_RMPPI, launchRMPPIShape<32>(a, stream, err));
-      err = "Robust MPPI rollout kernel is instantiated for 64 or 32 rollouts per block";
-      return MPPI_ERR_LAUNCH_SHAPE;
+      const int family = rmppiFamily(bx, pipeline);
+      if (family == MPPI_FAMILY_NONE)
+        return refuse(MPPI_ERR_LAUNCH_SHAPE, "Robust MPPI rollout kernel is instantiated for 64 or 32 rollouts per block", err);
+      return noted(family == MPPI_FAMILY_RMPPI_PIPELINE ? launchRMPPIPipeline(a, stream, err) :
+                   bx == 64                             ? launchRMPPIShape<64>(a, stream, err) :
+                                                          launchRMPPIShape<32>(a, stream, err),
+                   family, bx, 1, 2, false);
     }
     return ModelBase::launchRMPPI(bx, pipeline, a, s, stream, err);
   }
@@ -392,13 +424,13 @@ struct ModelT : ModelBase
   }
   /** does the instantiation ask for role-separated kernels (the one-lane pipeline, or the replicated-lane one), and do the
    *  classes those kernels would run say that their per-step methods hold no block barrier? */
-  static constexpr bool ROLE_SEPARATED = PIPELINE || !std::is_void<DYN_FAST_T>::value;
+  static constexpr bool ROLE_SEPARATED = PIPELINE || HAS_REP;
   static constexpr bool fastDeclared()
   {
-    if constexpr (std::is_void<DYN_FAST_T>::value)
+    if constexpr (!HAS_REP)
       return true;
     else
-      return mppi::barrier_free_step<DYN_FAST_T>::value;
+      return mppi::barrier_free_step<REP_T>::value;
   }
   static constexpr bool BARRIER_FREE_DECLARED = (!PIPELINE || mppi::barrier_free_step<DYN_T>::value) && fastDeclared() &&
                                                 (!ROLE_SEPARATED || (mppi::barrier_free_step<COST_T>::value &&
@@ -425,92 +457,17 @@ struct ModelT : ModelBase
   }
   bool supportsPipelineRep(int bx, int by, int bz) const override
   {
-    if constexpr (!std::is_void<DYN_FAST_T>::value)
-      return bx == 64 && bz == 1 && by == kernels::replicated_lanes<DYN_FAST_T>::value && hasShape(FAST_SHAPES{}, bx, by, bz);
+    if constexpr (HAS_REP)
+      return bx == 64 && bz == 1 && by == kernels::replicated_lanes<REP_T>::value && hasShape(FAST_SHAPES{}, bx, by, bz);
     return false;
   }
   bool fastShapeRefused(int bx, int by, int bz) const override
   {
-    if constexpr (has_register_form<DYN_T>::value && !std::is_void<DYN_FAST_T>::value)
-      return !dyn.register_form_ && hasShape(FAST_SHAPES{}, bx, by, bz);
-    return false;
+    return HAS_REP && !repUsable() && hasShape(FAST_SHAPES{}, bx, by, bz);
   }
-  template <class FAST = DYN_FAST_T>
-  mppi_status launchPipelineRep(const kernels::RolloutArgs& args, hipStream_t stream, std::string& err)
-  {
-    if constexpr (!std::is_void<FAST>::value)
-    {
-      FAST fast(dyn);
-      constexpr int REP = kernels::replicated_lanes<FAST>::value;
-      const int grid = (args.num_rollouts + 63) / 64;
-      const bool in_loop = SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
-      const int ring = kernels::pipelineRepRingSteps(fast, cost, smp, MAX_LDS_BYTES);
-      if (ring == 0)
-      {
-        err = "pipeline rollout kernel: the sample rows leave no room for the output ring in 160 KiB of LDS";
-        return MPPI_ERR_LDS_OVERFLOW;
-      }
-      const size_t smem = kernels::pipelineRepSharedBytes(fast, cost, smp, ring);
-      auto kfn = in_loop ? kernels::rolloutPipelineRepKernel<FAST, COST_T, SAMPLING_T, SAMPLING_T::IN_LOOP_DRAW>
-                         : kernels::rolloutPipelineRepKernel<FAST, COST_T, SAMPLING_T, false>;
-      if constexpr (SAMPLING_T::SUPPORTS_GLOBAL_ROWS)
-      {
-        if (smp.rows_global_d_)  // long horizons: the sample rows in HBM
-          kfn = in_loop ? kernels::rolloutPipelineRepKernel<FAST, COST_T, SAMPLING_T, SAMPLING_T::IN_LOOP_DRAW, true>
-                        : kernels::rolloutPipelineRepKernel<FAST, COST_T, SAMPLING_T, false, true>;
-      }
-      constexpr int WAVES = REP + kernels::PIPE_REP_SAMPLERS + kernels::PIPE_REP_COSTS;  // dynamics + helper waves
-      return launchChecked("rolloutPipelineRepKernel", kfn, dim3(grid), dim3(64 * WAVES, 1, 1), smem, stream, err, fast, cost, smp,
-                           args, ring);
-    }
-    err = "model has no replicated-lane dynamics";
-    return MPPI_ERR_LAUNCH_SHAPE;
-  }
-
   bool supportsPipelineFold(int bx, int by, int bz) const override
   {
     return PIPELINE && bx == 32 && by == 1 && bz == 2;
-  }
-  template <int Z, bool FOLD = false>
-  mppi_status launchPipeline(const kernels::RolloutArgs& args, hipStream_t stream, std::string& err)
-  {
-    if constexpr (PIPELINE)
-    {
-      const size_t smem = kernels::pipelineSharedBytes(dyn, cost, smp, Z, FOLD);
-      if (smem > MAX_LDS_BYTES)
-        return ldsOverflow("pipeline rollout kernel", smem, err);
-      const bool in_loop = SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
-      auto kfn = in_loop ? kernels::rolloutPipelineKernel<DYN_T, COST_T, SAMPLING_T, Z, SAMPLING_T::IN_LOOP_DRAW, FOLD>
-                         : kernels::rolloutPipelineKernel<DYN_T, COST_T, SAMPLING_T, Z, false, FOLD>;
-      if constexpr (SAMPLING_T::SUPPORTS_GLOBAL_ROWS)
-      {
-        if (smp.rows_global_d_)  // long horizons: the sample rows in HBM
-          kfn = in_loop ? kernels::rolloutPipelineKernel<DYN_T, COST_T, SAMPLING_T, Z, SAMPLING_T::IN_LOOP_DRAW, FOLD, true>
-                        : kernels::rolloutPipelineKernel<DYN_T, COST_T, SAMPLING_T, Z, false, FOLD, true>;
-      }
-      if constexpr (Z == 1 && !FOLD && SAMPLING_T::IN_LOOP_DRAW && !SAMPLING_T::COLORED)
-      {
-        // the previous iteration's block records merged by this launch's sampler waves (RolloutArgs::prev_records_d)
-        if (args.prev_records_d && args.prev_records_t_d && in_loop && !smp.rows_global_d_)
-          kfn = kernels::rolloutPipelineKernel<DYN_T, COST_T, SAMPLING_T, 1, SAMPLING_T::IN_LOOP_DRAW, false, false, true>;
-        else if (args.prev_records_d)
-        {
-          err = "prev_records_d: this launch cannot merge the previous records itself (noise source / rows in HBM / no transposed copy)";
-          return MPPI_ERR_STATE;
-        }
-      }
-      else if (args.prev_records_d)
-      {
-        err = "prev_records_d: the streamed merge exists for one-system Gaussian pipeline launches only";
-        return MPPI_ERR_STATE;
-      }
-      constexpr int RPB = FOLD ? 64 / Z : 64;  // rollouts per block
-      const int grid = (args.num_rollouts + RPB - 1) / RPB;
-      return launchChecked("rolloutPipelineKernel", kfn, dim3(grid), dim3(kernels::pipelineBlockX(Z, FOLD), 1, FOLD ? 1 : Z), smem,
-                           stream, err, dyn, cost, smp, args);
-    }
-    err = "model is not registered for the pipeline variant";
-    return MPPI_ERR_LAUNCH_SHAPE;
   }
 
   DYN_T dyn;
@@ -953,10 +910,7 @@ struct ModelT : ModelBase
   mppi_status launchNoiseDump(const SamplerLaunchState& s, float* out_d, hipStream_t stream, std::string& err) override
   {
     if (SAMPLING_T::IN_LOOP_DRAW && !s.eps_d)
-    {
-      err = "noise dump: this sampler draws inside the step loop; use mppi_philox_normal for its stream";
-      return MPPI_ERR_UNSUPPORTED;
-    }
+      return refuse(MPPI_ERR_UNSUPPORTED, "noise dump: this sampler draws inside the step loop; use mppi_philox_normal for its stream", err);
     prepSampler(s);
     mppi_status st = prepBasis(s, stream, err);
     if (st != MPPI_OK)
@@ -966,37 +920,27 @@ struct ModelT : ModelBase
     dump_smp.rows_global_d_ = nullptr;  // the dump kernel reads the rows back from ITS LDS, whatever the rollouts use
     const size_t smem = calcClassSharedMemSize(&dump_smp, 64);
     if (smem > MAX_LDS_BYTES)
-    {
-      err = "noise dump kernel: the rows of 64 rollouts do not fit the LDS at this horizon";
-      return MPPI_ERR_LDS_OVERFLOW;
-    }
+      return refuse(MPPI_ERR_LDS_OVERFLOW, "noise dump kernel: the rows of 64 rollouts do not fit the LDS at this horizon", err);
     return launchChecked("noiseDumpKernel", kernels::noiseDumpKernel<SAMPLING_T>, dim3((s.num_rollouts_local + 63) / 64),
                          dim3(64, 1, 1), smem, stream, err, dump_smp, out_d);
   }
 
-  template <int X, int Y, int Z, class... Rest>
-  static bool hasShape(Shapes<Shape<X, Y, Z>, Rest...>, int bx, int by, int bz)
+  template <class LIST>
+  static bool hasShape(LIST list, int bx, int by, int bz)
   {
-    return (bx == X && by == Y && bz == Z) || hasShape(Shapes<Rest...>{}, bx, by, bz);
-  }
-  static bool hasShape(Shapes<>, int, int, int)
-  {
-    return false;
+    return forShape(list, bx, by, bz, [](auto) {});
   }
   bool supportsShape(int bx, int by, int bz) const override
   {
     return hasShape(SHAPES{}, bx, by, bz) || hasShape(FAST_SHAPES{}, bx, by, bz);
   }
-  template <int X, int Y, int Z, class... Rest>
-  static void appendShapes(Shapes<Shape<X, Y, Z>, Rest...>, std::vector<int>& out)
+  template <class LIST>
+  static void appendShapes(LIST list, std::vector<int>& out)
   {
-    out.push_back(X);
-    out.push_back(Y);
-    out.push_back(Z);
-    appendShapes(Shapes<Rest...>{}, out);
-  }
-  static void appendShapes(Shapes<>, std::vector<int>&)
-  {
+    anyShape(list, [&](auto s) {
+      out.insert(out.end(), {s.x, s.y, s.z});
+      return false;
+    });
   }
   void listShapes(std::vector<int>& out) const override
   {
@@ -1036,179 +980,232 @@ struct ModelT : ModelBase
     if constexpr (SAMPLING_T::SUPPORTS_GLOBAL_ROWS)
       smp.rows_global_d_ = rows_d;
   }
+
+  /* ---- the rollout launch: one decision of the family, one function per family for its block; rolloutSharedBytes (what
+   *  planLaunch decides on) and launchRollout both go through them ---- */
+  /** the family of a rollout launch, in order of precedence; MPPI_FAMILY_NONE: the shape is not instantiated */
+  int rolloutFamily(int bx, int by, int bz, bool pipeline) const
+  {
+    if (pipeline)
+      return ModelT::supportsPipelineRep(bx, by, bz)  ? MPPI_FAMILY_PIPELINE_REP :
+             ModelT::supportsPipelineFold(bx, by, bz) ? MPPI_FAMILY_PIPELINE_FOLD :
+                                                        MPPI_FAMILY_PIPELINE;
+    if (HAS_REP && hasShape(FAST_SHAPES{}, bx, by, bz))
+      return MPPI_FAMILY_FUSED_REP;
+    return hasShape(SHAPES{}, bx, by, bz) ? MPPI_FAMILY_FUSED : MPPI_FAMILY_NONE;
+  }
+  /** ring 0, MAX_LDS_BYTES + 1 bytes: the sample rows leave no room for the output ring */
+  template <class FAST>
+  BlockPlan<> pipelineRepPlan(const FAST& fast) const
+  {
+    const int ring = kernels::pipelineRepRingSteps(fast, cost, smp, MAX_LDS_BYTES);
+    constexpr int WAVES = kernels::replicated_lanes<FAST>::value + kernels::PIPE_REP_SAMPLERS + kernels::PIPE_REP_COSTS;
+    return {ring ? kernels::pipelineRepSharedBytes(fast, cost, smp, ring) : MAX_LDS_BYTES + 1, dim3(64 * WAVES, 1, 1), 64, ring};
+  }
+  BlockPlan<> pipelinePlan(int z, bool fold) const
+  {
+    return {kernels::pipelineSharedBytes(dyn, cost, smp, z, fold), dim3(kernels::pipelineBlockX(z, fold), 1, fold ? 1 : z),
+            fold ? 64 / z : 64, 0};
+  }
+  /** rolloutKernel on one form: `by` contract lanes, each rollout on replicated_lanes<FORM_T> lanes of x */
+  template <class FORM_T>
+  BlockPlan<> fusedPlan(const FORM_T& form, int bx, int by, int bz) const
+  {
+    return {kernels::rolloutSharedBytes(form, cost, smp, bx, by, bz), dim3(bx * kernels::replicated_lanes<FORM_T>::value, by, bz), bx, 0};
+  }
   size_t rolloutSharedBytes(int bx, int by, int bz, int T, int D, bool pipeline) override
   {
     smp.params_.num_timesteps = T;
     smp.params_.num_distributions = D;
-    if constexpr (!std::is_void<DYN_FAST_T>::value)
+    const int family = rolloutFamily(bx, by, bz, pipeline);
+    if constexpr (HAS_REP)
     {
-      if (pipeline && supportsPipelineRep(bx, by, bz))
+      if (family == MPPI_FAMILY_PIPELINE_REP || family == MPPI_FAMILY_FUSED_REP)
       {
-        DYN_FAST_T fast(dyn);
-        const int ring = kernels::pipelineRepRingSteps(fast, cost, smp, MAX_LDS_BYTES);
-        return ring > 0 ? kernels::pipelineRepSharedBytes(fast, cost, smp, ring) : MAX_LDS_BYTES + 1;
+        REP_T rep(dyn);
+        return family == MPPI_FAMILY_PIPELINE_REP ? pipelineRepPlan(rep).smem : fusedPlan(rep, bx, 1, bz).smem;
       }
     }
-    if (pipeline)
-      return kernels::pipelineSharedBytes(dyn, cost, smp, bz, supportsPipelineFold(bx, by, bz));
-    if constexpr (!std::is_void<DYN_FAST_T>::value)
+    return pipeline ? pipelinePlan(bz, family == MPPI_FAMILY_PIPELINE_FOLD).smem : fusedPlan(dyn, bx, by, bz).smem;
+  }
+
+  template <class FAST = REP_T>
+  mppi_status launchPipelineRep(const kernels::RolloutArgs& args, hipStream_t stream, std::string& err)
+  {
+    if constexpr (!std::is_void<FAST>::value)
     {
-      if (hasShape(FAST_SHAPES{}, bx, by, bz))
+      FAST fast(dyn);
+      const BlockPlan<> p = pipelineRepPlan(fast);
+      if (p.ring == 0)
+        return refuse(MPPI_ERR_LDS_OVERFLOW,
+                      "pipeline rollout kernel: the sample rows leave no room for the output ring in 160 KiB of LDS", err);
+      auto kfn = kernelVariant<true>([](auto draw, auto hbm) {
+        return kernels::rolloutPipelineRepKernel<FAST, COST_T, SAMPLING_T, decltype(draw)::value, decltype(hbm)::value>;
+      });
+      return launchChecked("rolloutPipelineRepKernel", kfn, p.grid(args.num_rollouts), p.block, p.smem, stream, err, fast, cost, smp,
+                           args, p.ring);
+    }
+    return refuse(MPPI_ERR_LAUNCH_SHAPE, "model has no replicated-lane dynamics", err);
+  }
+  template <int Z, bool FOLD = false>
+  mppi_status launchPipeline(const kernels::RolloutArgs& args, hipStream_t stream, std::string& err)
+  {
+    if constexpr (PIPELINE)
+    {
+      const BlockPlan<> p = pipelinePlan(Z, FOLD);
+      if (p.smem > MAX_LDS_BYTES)
+        return ldsOverflow("pipeline rollout kernel", p.smem, err);
+      auto kfn = kernelVariant<true>([](auto draw, auto hbm) {
+        return kernels::rolloutPipelineKernel<DYN_T, COST_T, SAMPLING_T, Z, decltype(draw)::value, FOLD, decltype(hbm)::value>;
+      });
+      if constexpr (Z == 1 && !FOLD && SAMPLING_T::IN_LOOP_DRAW && !SAMPLING_T::COLORED)
       {
-        DYN_FAST_T fast(dyn);
-        return kernels::rolloutSharedBytes(fast, cost, smp, bx, 1, bz);
+        // the previous iteration's block records merged by this launch's sampler waves (RolloutArgs::prev_records_d)
+        if (args.prev_records_d && args.prev_records_t_d && drawsInLoop() && !smp.rows_global_d_)
+          kfn = kernels::rolloutPipelineKernel<DYN_T, COST_T, SAMPLING_T, 1, SAMPLING_T::IN_LOOP_DRAW, false, false, true>;
+        else if (args.prev_records_d)
+          return refuse(MPPI_ERR_STATE,
+                        "prev_records_d: this launch cannot merge the previous records itself (noise source / rows in HBM / no "
+                        "transposed copy)",
+                        err);
       }
+      else if (args.prev_records_d)
+        return refuse(MPPI_ERR_STATE, "prev_records_d: the streamed merge exists for one-system Gaussian pipeline launches only", err);
+      return launchChecked("rolloutPipelineKernel", kfn, p.grid(args.num_rollouts), p.block, p.smem, stream, err, dyn, cost, smp, args);
     }
-    return kernels::rolloutSharedBytes(dyn, cost, smp, bx, by, bz);
+    return refuse(MPPI_ERR_LAUNCH_SHAPE, "model is not registered for the pipeline variant", err);
   }
-
-  /** fast variant: shape (X, REP, Z) runs as X rollouts x REP replicated lanes with one contract lane (BY = 1) */
-  template <int X, int Y, int Z, class FAST = DYN_FAST_T>
-  mppi_status launchFastShape(const kernels::RolloutArgs& args, hipStream_t stream, std::string& err)
+  /** rolloutKernel for one registered shape on `form`.  The replicated-lane form runs shape (X, REP, Z) as X rollouts x REP
+   *  replicated lanes with one contract lane (BY = 1).  The in-loop Philox draw needs one lane per rollout; otherwise the rows are
+   *  pre-filled by initializeDistributions. */
+  template <class SHAPE, class FORM_T>
+  mppi_status launchFused(SHAPE, FORM_T& form, const kernels::RolloutArgs& args, hipStream_t stream, std::string& err)
   {
-    FAST fast(dyn);
-    constexpr int REP = kernels::replicated_lanes<FAST>::value;
-    static_assert(REP == Y, "fast shape: BY must equal the plugin's REPLICATED_LANES");
-    const size_t smem = kernels::rolloutSharedBytes(fast, cost, smp, X, 1, Z);
-    if (smem > MAX_LDS_BYTES)
-      return ldsOverflow("rollout kernel", smem, err);
-    const bool in_loop = SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
-    auto kfn = in_loop ? kernels::rolloutKernel<FAST, COST_T, SAMPLING_T, X, 1, Z, SAMPLING_T::IN_LOOP_DRAW>
-                       : kernels::rolloutKernel<FAST, COST_T, SAMPLING_T, X, 1, Z, false>;
-    const int grid = (args.num_rollouts + X - 1) / X;
-    return launchChecked("rolloutKernel (fast variant)", kfn, dim3(grid), dim3(X * REP, 1, Z), smem, stream, err, fast, cost, smp,
-                         args);
+    constexpr bool OWN = std::is_same<FORM_T, DYN_T>::value;
+    constexpr int X = SHAPE::x, BY = OWN ? SHAPE::y : 1, Z = SHAPE::z;
+    static_assert(OWN || kernels::replicated_lanes<FORM_T>::value == SHAPE::y, "fast shape: BY must equal the plugin's REPLICATED_LANES");
+    const BlockPlan<> p = fusedPlan(form, X, BY, Z);
+    if (p.smem > MAX_LDS_BYTES)
+      return ldsOverflow("rollout kernel", p.smem, err);
+    auto kfn = kernelVariant<false, (BY == 1) && SAMPLING_T::IN_LOOP_DRAW>([](auto draw, auto) {
+      return kernels::rolloutKernel<FORM_T, COST_T, SAMPLING_T, X, BY, Z, decltype(draw)::value>;
+    });
+    return launchChecked(OWN ? "rolloutKernel" : "rolloutKernel (fast variant)", kfn, p.grid(args.num_rollouts), p.block, p.smem, stream,
+                         err, form, cost, smp, args);
   }
-  template <int X, int Y, int Z, class... Rest>
-  mppi_status dispatchFast(Shapes<Shape<X, Y, Z>, Rest...>, int bx, int by, int bz, const kernels::RolloutArgs& args,
-                           hipStream_t stream, std::string& err, bool& handled)
-  {
-    if (bx == X && by == Y && bz == Z)
-    {
-      handled = true;
-      return launchFastShape<X, Y, Z>(args, stream, err);
-    }
-    return dispatchFast(Shapes<Rest...>{}, bx, by, bz, args, stream, err, handled);
-  }
-  mppi_status dispatchFast(Shapes<>, int, int, int, const kernels::RolloutArgs&, hipStream_t, std::string&, bool& handled)
-  {
-    handled = false;
-    return MPPI_OK;
-  }
-
-  template <int X, int Y, int Z>
-  mppi_status launchShape(const kernels::RolloutArgs& args, hipStream_t stream, std::string& err)
-  {
-    const size_t smem = kernels::rolloutSharedBytes(dyn, cost, smp, X, Y, Z);
-    if (smem > MAX_LDS_BYTES)
-      return ldsOverflow("rollout kernel", smem, err);
-    // in-loop Philox draw needs one lane per rollout; otherwise the rows are pre-filled by initializeDistributions
-    const bool in_loop = (Y == 1) && SAMPLING_T::IN_LOOP_DRAW && smp.noise_source_ == 0;
-    auto kfn = in_loop ? kernels::rolloutKernel<DYN_T, COST_T, SAMPLING_T, X, Y, Z, (Y == 1) && SAMPLING_T::IN_LOOP_DRAW>
-                       : kernels::rolloutKernel<DYN_T, COST_T, SAMPLING_T, X, Y, Z, false>;
-    const int grid = (args.num_rollouts + X - 1) / X;
-    return launchChecked("rolloutKernel", kfn, dim3(grid), dim3(X, Y, Z), smem, stream, err, dyn, cost, smp, args);
-  }
-
-  template <int X, int Y, int Z, class... Rest>
-  mppi_status dispatch(Shapes<Shape<X, Y, Z>, Rest...>, int bx, int by, int bz, const kernels::RolloutArgs& args,
-                       hipStream_t stream, std::string& err)
-  {
-    if (bx == X && by == Y && bz == Z)
-      return launchShape<X, Y, Z>(args, stream, err);
-    return dispatch(Shapes<Rest...>{}, bx, by, bz, args, stream, err);
-  }
-  mppi_status dispatch(Shapes<>, int bx, int by, int bz, const kernels::RolloutArgs&, hipStream_t, std::string& err)
-  {
-    err = "block shape (" + std::to_string(bx) + "," + std::to_string(by) + "," + std::to_string(bz) +
-          ") is not instantiated for this model";
-    return MPPI_ERR_LAUNCH_SHAPE;
-  }
-
   mppi_status launchRollout(int bx, int by, int bz, bool pipeline, const kernels::RolloutArgs& args,
                             const SamplerLaunchState& s, hipStream_t stream, std::string& err) override
   {
     if (!blobsReady(err))
       return MPPI_ERR_STATE;
     prepSampler(s);
-    {
-      mppi_status st = prepBasis(s, stream, err);
-      if (st != MPPI_OK)
-        return st;
-    }
-    if constexpr (has_register_form<DYN_T>::value && !std::is_void<DYN_FAST_T>::value)
-    {
-      if (!dyn.register_form_ && hasShape(FAST_SHAPES{}, bx, by, bz))
-      {
-        err = "the replicated-lane block shapes of this model exist for its default network shape only: create the "
-              "controller with block_y = 1 for a network set through 'lstm_structure'";
-        return MPPI_ERR_LAUNCH_SHAPE;
-      }
-    }
-    auto noted = [&](int family, mppi_status st) {
-      if (st == MPPI_OK)
-        last_launch = LaunchRecord{family, bx, by, bz, smp.rows_global_d_ != nullptr, args.prev_records_d != nullptr};
+    mppi_status st = prepBasis(s, stream, err);
+    if (st != MPPI_OK)
       return st;
-    };
-    if (pipeline && supportsPipelineRep(bx, by, bz))
-      return noted(MPPI_FAMILY_PIPELINE_REP, launchPipelineRep(args, stream, err));
-    if (pipeline && supportsPipelineFold(bx, by, bz))
-      return noted(MPPI_FAMILY_PIPELINE_FOLD, launchPipeline<2, true>(args, stream, err));
-    if (pipeline)
-      return noted(MPPI_FAMILY_PIPELINE, bz == 1 ? launchPipeline<1>(args, stream, err) : launchPipeline<2>(args, stream, err));
-    if constexpr (!std::is_void<DYN_FAST_T>::value)
+    if (ModelT::fastShapeRefused(bx, by, bz))
+      return refuse(MPPI_ERR_LAUNCH_SHAPE,
+                    "the replicated-lane block shapes of this model exist for its default network shape only: create the "
+                    "controller with block_y = 1 for a network set through 'lstm_structure'",
+                    err);
+    const int family = rolloutFamily(bx, by, bz, pipeline);
+    switch (family)
     {
-      bool handled = false;
-      mppi_status st = dispatchFast(FAST_SHAPES{}, bx, by, bz, args, stream, err, handled);
-      if (handled)
-        return noted(MPPI_FAMILY_FUSED_REP, st);
+      case MPPI_FAMILY_PIPELINE_REP:
+        st = launchPipelineRep(args, stream, err);
+        break;
+      case MPPI_FAMILY_PIPELINE_FOLD:
+        st = launchPipeline<2, true>(args, stream, err);
+        break;
+      case MPPI_FAMILY_PIPELINE:
+        st = bz == 1 ? launchPipeline<1>(args, stream, err) : launchPipeline<2>(args, stream, err);
+        break;
+      case MPPI_FAMILY_FUSED_REP:
+        if constexpr (HAS_REP)
+          forShape(FAST_SHAPES{}, bx, by, bz, [&](auto shape) {
+            REP_T rep(dyn);
+            st = launchFused(shape, rep, args, stream, err);
+          });
+        break;
+      case MPPI_FAMILY_FUSED:
+        forShape(SHAPES{}, bx, by, bz, [&](auto shape) { st = launchFused(shape, dyn, args, stream, err); });
+        break;
+      default:
+        err = "block shape (" + std::to_string(bx) + "," + std::to_string(by) + "," + std::to_string(bz) +
+              ") is not instantiated for this model";
+        return MPPI_ERR_LAUNCH_SHAPE;
     }
-    return noted(MPPI_FAMILY_FUSED, dispatch(SHAPES{}, bx, by, bz, args, stream, err));
+    return noted(st, family, bx, by, bz, args.prev_records_d != nullptr);
   }
 
+  /* ---- the single-rollout kernels (the trajectory re-roll of launchFinalize, launchReplay): a chain of T dependent steps, what
+   *  counts is the length of a step's dependent chain ---- */
+  enum SingleForm
+  {
+    FORM_WAVE,  ///< ONE rollout on a wave (HAS_WAVE); MPPI_AMD_FINALIZE_FORM=rep skips it — tests compare the two
+    FORM_REP,   ///< the replicated-lane form: the register-resident single-wave variant
+    FORM_OWN    ///< the model itself on FIN_BY contract lanes
+  };
+  /** The one choice of the form such a kernel runs on: the wave form, else the replicated-lane form if it is usable, each when
+   *  its block fits the LDS, else the model itself.  bytes(form, which) is the block's LDS request on a form, launch(form, which,
+   *  smem) launches on the chosen one; `which` is a std::integral_constant of SingleForm. */
+  template <class BYTES, class LAUNCH>
+  mppi_status onSingleRolloutForm(BYTES&& bytes, LAUNCH&& launch)
+  {
+    if constexpr (HAS_WAVE)
+    {
+      const char* env = getenv("MPPI_AMD_FINALIZE_FORM");
+      if (!(env && env[0] == 'r'))
+      {
+        constexpr std::integral_constant<SingleForm, FORM_WAVE> which{};
+        typename REP_T::FINALIZE_FORM wave(dyn);
+        const size_t smem = bytes(wave, which);
+        if (smem <= MAX_LDS_BYTES)
+          return launch(wave, which, smem);
+      }
+    }
+    if constexpr (HAS_REP)
+    {
+      if (repUsable())
+      {
+        constexpr std::integral_constant<SingleForm, FORM_REP> which{};
+        REP_T rep(dyn);
+        const size_t smem = bytes(rep, which);
+        if (smem <= MAX_LDS_BYTES)
+          return launch(rep, which, smem);
+      }
+    }
+    constexpr std::integral_constant<SingleForm, FORM_OWN> which{};
+    return launch(dyn, which, bytes(dyn, which));
+  }
   mppi_status launchFinalize(int D, const kernels::FinalizeArgs& a, hipStream_t stream, std::string& err) override
   {
     if (!blobsReady(err))
       return MPPI_ERR_STATE;
-    if constexpr (has_finalize_form<DYN_FAST_T>::value)
-    {
-      // a form of the model made for ONE rollout on a wave (NN models: lane = neuron, utils/nn_helpers/fnn_wave.hpp): the
-      // re-rollout is a chain of T dependent steps, what counts is the length of a step's dependent chain
-      // (MPPI_AMD_FINALIZE_FORM=rep: the replicated-lane form instead — tests compare the two)
-      const char* form = getenv("MPPI_AMD_FINALIZE_FORM");
-      if (!(form && form[0] == 'r'))
-      {
-        using WAVE_T = typename DYN_FAST_T::FINALIZE_FORM;
-        WAVE_T wave_form(dyn);
-        const size_t smem_w = kernels::finalizeRepSharedBytes(wave_form, a.num_timesteps, a.scratch_d != nullptr);
-        if (smem_w <= MAX_LDS_BYTES)
-        {
-          auto kw = a.scratch_d ? kernels::finalizeRepKernel<WAVE_T, true> : kernels::finalizeRepKernel<WAVE_T, false>;
-          return launchChecked("finalizeRepKernel (wave form)", kw, dim3(D), dim3(64, 1, 1), smem_w, stream, err, wave_form, a);
-        }
-      }
-    }
-    if constexpr (!std::is_void<DYN_FAST_T>::value)
-    {  // replicated-lane (MFMA) dynamics: the register-resident single-wave variant
-      DYN_FAST_T fast(dyn);
-      const size_t smem_rep = kernels::finalizeRepSharedBytes(fast, a.num_timesteps, a.scratch_d != nullptr);
-      bool usable = smem_rep <= MAX_LDS_BYTES;
-      if constexpr (has_register_form<DYN_T>::value)
-        usable = usable && dyn.register_form_;
-      if (usable)
-      {
-        auto krep = a.scratch_d ? kernels::finalizeRepKernel<DYN_FAST_T, true> : kernels::finalizeRepKernel<DYN_FAST_T, false>;
-        return launchChecked("finalizeRepKernel", krep, dim3(D), dim3(64, 1, 1), smem_rep, stream, err, fast, a);
-      }
-    }
-    const size_t smem = kernels::finalizeSharedBytes(dyn, a.num_timesteps, FIN_BY, a.scratch_d != nullptr);
-    if (smem > MAX_LDS_BYTES)
-    {
-      err = "finalize kernel LDS overflow";
-      return MPPI_ERR_LDS_OVERFLOW;
-    }
-    auto kfn = a.scratch_d ? kernels::finalizeKernel<DYN_T, FIN_BY, true> : kernels::finalizeKernel<DYN_T, FIN_BY, false>;
-    return launchChecked("finalizeKernel", kfn, dim3(D), dim3(kernels::finalizeBlockX(FIN_BY), FIN_BY, 1), smem, stream, err, dyn, a);
+    const bool scratch = a.scratch_d != nullptr;
+    return onSingleRolloutForm(
+        [&](auto& form, auto which) {
+          if constexpr (decltype(which)::value == FORM_OWN)
+            return kernels::finalizeSharedBytes(form, a.num_timesteps, FIN_BY, scratch);
+          else
+            return kernels::finalizeRepSharedBytes(form, a.num_timesteps, scratch);
+        },
+        [&](auto& form, auto which, size_t smem) -> mppi_status {
+          using FORM_T = std::decay_t<decltype(form)>;
+          if constexpr (decltype(which)::value == FORM_OWN)
+          {
+            if (smem > MAX_LDS_BYTES)
+              return refuse(MPPI_ERR_LDS_OVERFLOW, "finalize kernel LDS overflow", err);
+            auto kfn = scratch ? kernels::finalizeKernel<FORM_T, FIN_BY, true> : kernels::finalizeKernel<FORM_T, FIN_BY, false>;
+            return launchChecked("finalizeKernel", kfn, dim3(D), dim3(kernels::finalizeBlockX(FIN_BY), FIN_BY, 1), smem, stream, err,
+                                 form, a);
+          }
+          else
+          {
+            auto kfn = scratch ? kernels::finalizeRepKernel<FORM_T, true> : kernels::finalizeRepKernel<FORM_T, false>;
+            return launchChecked(decltype(which)::value == FORM_WAVE ? "finalizeRepKernel (wave form)" : "finalizeRepKernel", kfn,
+                                 dim3(D), dim3(64, 1, 1), smem, stream, err, form, a);
+          }
+        });
   }
 
   /** plain one-wave finalize form only (FIN_BY == 1, no replicated-lane / wave form): what the one-lane pipeline models have */
@@ -1227,16 +1224,13 @@ struct ModelT : ModelBase
       if (!blobsReady(err))
         return MPPI_ERR_STATE;
       if (a.scratch_d || a.phases != 1 || ((a.num_timesteps * DYN_T::CONTROL_DIM) & 3) != 0 || m.num_records > 256)
-      {
-        err = "mergeControlKernel: control phase of a split hand-over, sequence in LDS, T*C a multiple of 4, <= 256 records";
-        return MPPI_ERR_LAUNCH_SHAPE;
-      }
+        return refuse(MPPI_ERR_LAUNCH_SHAPE,
+                      "mergeControlKernel: control phase of a split hand-over, sequence in LDS, T*C a multiple of 4, <= 256 records", err);
       const size_t smem = kernels::mergeControlSharedBytes(dyn, a.num_timesteps);
       return launchChecked("mergeControlKernel", kernels::mergeControlKernel<DYN_T>, dim3(1),
                            dim3(64 * kernels::MERGE_CONTROL_WAVES, 1, 1), smem, stream, err, dyn, a, m);
     }
-    err = "model has no merging control phase";
-    return MPPI_ERR_LAUNCH_SHAPE;
+    return refuse(MPPI_ERR_LAUNCH_SHAPE, "model has no merging control phase", err);
   }
 
   mppi_status launchModelStep(float* x_d, float* u_d, float dt, int enforce, hipStream_t stream,
@@ -1264,15 +1258,9 @@ struct ModelT : ModelBase
       // a model is the DYN_T here says where they are with gradWeights()
       if constexpr (has_grad_weights<DYN_T>::value)
         if (!dyn.gradWeights())
-        {
-          err = "model needs the 'dynamics_weights' blob (mppi_set_model_blob) before it can be linearised";
-          return MPPI_ERR_STATE;
-        }
+          return refuse(MPPI_ERR_STATE, "model needs the 'dynamics_weights' blob (mppi_set_model_blob) before it can be linearised", err);
       if (a.n < 1 || !a.x_d || !a.u_d || !a.A_d || !a.B_d)
-      {
-        err = "linearizeKernel: n >= 1 points and four device pointers";
-        return MPPI_ERR_INVALID_ARG;
-      }
+        return refuse(MPPI_ERR_INVALID_ARG, "linearizeKernel: n >= 1 points and four device pointers", err);
       const size_t smem = kernels::linearizeSharedBytes(dyn);
       constexpr int P = kernels::linearizeBlockPoints<DYN_T>();
       return launchChecked("linearizeKernel", kernels::linearizeKernel<DYN_T>, dim3((a.n + P - 1) / P),
@@ -1286,66 +1274,37 @@ struct ModelT : ModelBase
     if constexpr (mppi::has_compute_grad<DYN_T>::value)
     {
       if (a.T < 1 || !a.A_d || !a.B_d || !a.Q_d || !a.R_d || !a.Qf_d || !a.gains_d || !a.status_d)
-      {
-        err = "ddpBackwardKernel: T >= 1 steps and seven device pointers";
-        return MPPI_ERR_INVALID_ARG;
-      }
+        return refuse(MPPI_ERR_INVALID_ARG, "ddpBackwardKernel: T >= 1 steps and seven device pointers", err);
       return launchChecked("ddpBackwardKernel", kernels::ddpBackwardKernel<DYN_T::STATE_DIM, DYN_T::CONTROL_DIM>, dim3(1),
                            dim3(64, 1, 1), 0, stream, err, a);
     }
     return ModelBase::launchDdpBackward(a, stream, err);
   }
 
-  /** one form of replayKernel: `rd` is the dynamics object it takes (the model, or one of its replicated-lane forms), BY the
-   *  contract lanes per row */
-  template <int BY, class RD_T>
-  mppi_status launchReplayForm(const char* what, RD_T& rd, const SAMPLING_T& rs, const kernels::ReplayArgs& a, hipStream_t stream,
-                               std::string& err)
-  {
-    const size_t smem = kernels::replaySharedBytes(rd, cost, BY);
-    if (smem > MAX_LDS_BYTES)
-      return ldsOverflow(what, smem, err);
-    constexpr int ROWS = BY == 1 ? kernels::replayBlockRows<RD_T>() : 1;
-    return launchChecked(what, kernels::replayKernel<RD_T, COST_T, SAMPLING_T, BY>, dim3((a.n + ROWS - 1) / ROWS),
-                         dim3(BY == 1 ? 64 : 1, BY, 1), smem, stream, err, rd, cost, rs, a);
-  }
-  /** the form is chosen as launchFinalize chooses the re-roll's: the one-rollout-per-wave form of an NN model, else its
-   *  replicated-lane form, else the model itself with FIN_BY lanes */
+  /** replayKernel on the form launchFinalize's re-roll runs on (onSingleRolloutForm chooses for both) */
   mppi_status launchReplay(const kernels::ReplayArgs& a, const SamplerLaunchState& s, hipStream_t stream, std::string& err) override
   {
     if (!blobsReady(err))
       return MPPI_ERR_STATE;
     if (a.n < 1 || !a.x0_d || !a.optimal_d || !a.idx_d || !a.y_d || !a.cost_d || !a.crash_d)
-    {
-      err = "replayKernel: n >= 1 rows and six device pointers";
-      return MPPI_ERR_INVALID_ARG;
-    }
+      return refuse(MPPI_ERR_INVALID_ARG, "replayKernel: n >= 1 rows and six device pointers", err);
     // the sampler as the last rollout launch saw it, on a copy: the model's own keeps what that launch left in it
     const SAMPLING_T keep = smp;
     prepSampler(s);
     const SAMPLING_T rs = smp;
     smp = keep;
-    if constexpr (has_finalize_form<DYN_FAST_T>::value)
-    {
-      const char* form = getenv("MPPI_AMD_FINALIZE_FORM");
-      if (!(form && form[0] == 'r'))
-      {
-        using WAVE_T = typename DYN_FAST_T::FINALIZE_FORM;
-        WAVE_T wave_form(dyn);
-        if (kernels::replaySharedBytes(wave_form, cost, 1) <= MAX_LDS_BYTES)
-          return launchReplayForm<1>("replayKernel (wave form)", wave_form, rs, a, stream, err);
-      }
-    }
-    if constexpr (!std::is_void<DYN_FAST_T>::value)
-    {
-      DYN_FAST_T fast(dyn);
-      bool usable = kernels::replaySharedBytes(fast, cost, 1) <= MAX_LDS_BYTES;
-      if constexpr (has_register_form<DYN_T>::value)
-        usable = usable && dyn.register_form_;
-      if (usable)
-        return launchReplayForm<1>("replayKernel (replicated lanes)", fast, rs, a, stream, err);
-    }
-    return launchReplayForm<FIN_BY>("replayKernel", dyn, rs, a, stream, err);
+    return onSingleRolloutForm(
+        [&](auto& rd, auto which) { return kernels::replaySharedBytes(rd, cost, decltype(which)::value == FORM_OWN ? FIN_BY : 1); },
+        [&](auto& rd, auto which, size_t smem) -> mppi_status {
+          using RD_T = std::decay_t<decltype(rd)>;
+          constexpr int BY = decltype(which)::value == FORM_OWN ? FIN_BY : 1;  // contract lanes per row
+          const char* const what[] = {"replayKernel (wave form)", "replayKernel (replicated lanes)", "replayKernel"};
+          if (smem > MAX_LDS_BYTES)
+            return ldsOverflow(what[which], smem, err);
+          constexpr int ROWS = BY == 1 ? kernels::replayBlockRows<RD_T>() : 1;
+          return launchChecked(what[which], kernels::replayKernel<RD_T, COST_T, SAMPLING_T, BY>, dim3((a.n + ROWS - 1) / ROWS),
+                               dim3(BY == 1 ? 64 : 1, BY, 1), smem, stream, err, rd, cost, rs, a);
+        });
   }
 };
 

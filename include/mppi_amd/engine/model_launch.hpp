@@ -1,6 +1,7 @@
 /**
  * model_launch.hpp — the one path every kernel launch of ModelT (model_instance.hpp) takes, and what a launch site needs next to
- * it: the LDS size of a block, the refusal of a request beyond it, and the compile-time block shape lists.
+ * it: the LDS size of a block, the refusal of a request beyond it, what a launch family asks of a block (BlockPlan), and the
+ * compile-time block shape lists with the one walk over them (forShape).
  */
 #ifndef MPPI_AMD_MODEL_LAUNCH_HPP_
 #define MPPI_AMD_MODEL_LAUNCH_HPP_
@@ -47,12 +48,51 @@ constexpr size_t MAX_LDS_BYTES = 160 * 1024;  // gfx950: 160 KiB per CU, one wor
 template <int X, int Y, int Z>
 struct Shape
 {
+  static constexpr int x = X, y = Y, z = Z;
 };
 template <class... S>
 struct Shapes
 {
 };
+/** f(Shape<X, Y, Z>{}) for the shapes of a list, in its order, until a call returns true; false: none did */
+template <class... S, class F>
+inline bool anyShape(Shapes<S...>, F&& f)
+{
+  return (f(S{}) || ...);
+}
+/** for the shape of the list equal to (bx, by, bz): f(Shape<X, Y, Z>{}), X, Y, Z compile-time through its type; false: no such shape */
+template <class LIST, class F>
+inline bool forShape(LIST list, int bx, int by, int bz, F&& f)
+{
+  return anyShape(list, [&](auto s) {
+    if (bx != s.x || by != s.y || bz != s.z)
+      return false;
+    f(s);
+    return true;
+  });
+}
 
+/** what a launch family asks of a block, from the one function both the LDS query and the launch go through: LDS bytes, threads,
+ *  rollouts per block and, for the role-pipelined families, the ring(s) — none (0 steps) when not even the shortest fits */
+template <class RING = int>
+struct BlockPlan
+{
+  size_t smem;
+  dim3 block;
+  int rollouts;
+  RING ring;
+  dim3 grid(int num_rollouts) const
+  {
+    return dim3((num_rollouts + rollouts - 1) / rollouts);
+  }
+};
+
+/** a launch function's refusal: the reason into `err`, the status back */
+inline mppi_status refuse(mppi_status st, const char* why, std::string& err)
+{
+  err = why;
+  return st;
+}
 /** "<what> needs N B of LDS per block; gfx950 has 163840" */
 inline mppi_status ldsOverflow(const char* what, size_t smem, std::string& err)
 {
