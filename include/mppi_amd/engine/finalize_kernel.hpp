@@ -207,12 +207,7 @@ template <class DYN_T, int BY, bool SCRATCH = false>
 __global__ void __launch_bounds__(BY* finalizeBlockX(BY)) finalizeKernel(DYN_T dynamics_obj, const FinalizeArgs a)
 {
   constexpr int LX = finalizeBlockX(BY);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_x() == LX);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_y() == BY);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_z() == 1);
-  __builtin_assume(__builtin_amdgcn_workitem_id_x() < LX);
-  __builtin_assume(__builtin_amdgcn_workitem_id_y() < BY);
-  __builtin_assume(__builtin_amdgcn_workitem_id_z() == 0);
+  MPPI_ASSUME_BLOCK_SHAPE(LX, BY, 1);
   DYN_T* dynamics = &dynamics_obj;
   constexpr int S = DYN_T::STATE_DIM, C = DYN_T::CONTROL_DIM, O = DYN_T::OUTPUT_DIM;
   const int T = a.num_timesteps;

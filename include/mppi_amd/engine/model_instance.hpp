@@ -44,12 +44,7 @@ namespace engine
 template <class DYN_T, int BY>
 __global__ void __launch_bounds__(BY) modelStepKernel(DYN_T dynamics_obj, float* x_d, float* u_d, float dt, int enforce)
 {
-  __builtin_assume(__builtin_amdgcn_workgroup_size_x() == 1);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_y() == BY);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_z() == 1);
-  __builtin_assume(__builtin_amdgcn_workitem_id_x() == 0);
-  __builtin_assume(__builtin_amdgcn_workitem_id_y() < BY);
-  __builtin_assume(__builtin_amdgcn_workitem_id_z() == 0);
+  MPPI_ASSUME_BLOCK_SHAPE(1, BY, 1);
   DYN_T* dynamics = &dynamics_obj;
   constexpr int S = DYN_T::STATE_DIM, C = DYN_T::CONTROL_DIM, O = DYN_T::OUTPUT_DIM;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];

@@ -77,12 +77,7 @@ __global__ void __launch_bounds__(BY == 1 ? 64 : BY)
   static_assert(REP == 1 || BY == 1, "replicated lanes run with one contract lane");
   static_assert(64 % REP == 0, "a wave holds whole rows");
   constexpr int LX = BY == 1 ? 64 : 1;
-  __builtin_assume(__builtin_amdgcn_workgroup_size_x() == LX);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_y() == BY);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_z() == 1);
-  __builtin_assume(__builtin_amdgcn_workitem_id_x() < LX);
-  __builtin_assume(__builtin_amdgcn_workitem_id_y() < BY);
-  __builtin_assume(__builtin_amdgcn_workitem_id_z() == 0);
+  MPPI_ASSUME_BLOCK_SHAPE(LX, BY, 1);
   DYN_T* dynamics = &dynamics_obj;
   COST_T* costs = &costs_obj;
   SAMPLING_T* sampling = &sampling_obj;

@@ -81,12 +81,7 @@ __global__ void __launch_bounds__(BX* replicated_lanes<DYN_T>::value)
 {
   constexpr int REP = replicated_lanes<DYN_T>::value;
   static_assert(REP == 1 || (64 % REP == 0 && (BX * REP) % 64 == 0), "replicated lanes need whole waves");
-  __builtin_assume(__builtin_amdgcn_workgroup_size_x() == BX * REP);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_y() == 1);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_z() == 1);
-  __builtin_assume(__builtin_amdgcn_workitem_id_x() < BX * REP);
-  __builtin_assume(__builtin_amdgcn_workitem_id_y() == 0);
-  __builtin_assume(__builtin_amdgcn_workitem_id_z() == 0);
+  MPPI_ASSUME_BLOCK_SHAPE(BX * REP, 1, 1);
   DYN_T* dynamics = &dynamics_obj;
   COST_T* costs = &costs_obj;
   SAMPLING_T* sampling = &sampling_obj;
@@ -176,12 +171,7 @@ __global__ void __launch_bounds__(BX * 2 * replicated_lanes<DYN_T>::value)
   // the dynamics plugin; blockDim.x = BX * REP, everything else is evaluated redundantly on the replicas
   constexpr int REP = replicated_lanes<DYN_T>::value;
   static_assert(REP == 1 || (64 % REP == 0 && (BX * REP) % 64 == 0), "replicated lanes need whole waves");
-  __builtin_assume(__builtin_amdgcn_workgroup_size_x() == BX * REP);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_y() == 1);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_z() == BZ);
-  __builtin_assume(__builtin_amdgcn_workitem_id_x() < BX * REP);
-  __builtin_assume(__builtin_amdgcn_workitem_id_y() == 0);
-  __builtin_assume(__builtin_amdgcn_workitem_id_z() < BZ);
+  MPPI_ASSUME_BLOCK_SHAPE(BX * REP, 1, BZ);
   const RolloutArgs& args = rargs.base;
   DYN_T* dynamics = &dynamics_obj;
   COST_T* costs = &costs_obj;

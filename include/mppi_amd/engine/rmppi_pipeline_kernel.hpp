@@ -19,7 +19,7 @@
  *                           rolloutPipelineRepKernel; they also write the fed-back, clamped control back into the sample
  *                           row (rmppi_kernels.cu:780-781) — one instruction per 64 rollouts
  *
- * coupled by monotonic progress counters in LDS (rollout_pipeline_kernel.hpp).  The block-wide barrier per step is gone:
+ * coupled by monotonic progress counters in LDS (pipe_roles.hpp).  The block-wide barrier per step is gone:
  * the real wave of a group of rollouts waits for the nominal wave of the same rollouts only (it trails it by one pair of
  * steps), through a ring of nominal states.  Every rollout is evaluated with the plugin calls, in the order, of
  * rolloutRMPPIKernel: trajectory costs and control updates are the same bits (tests/test_rmppi.py compares the two).
@@ -33,6 +33,7 @@
 #include "rmppi_kernels.hpp"
 #include "rollout_pipeline_kernel.hpp"
 #include "kernarg_view.hpp"
+#include "pipe_roles.hpp"
 
 namespace mppi
 {
@@ -206,12 +207,7 @@ __global__ void __launch_bounds__(64 * rmppiPipelineWaves<DYN_T>())
   constexpr int NWAVES = rmppiPipelineWaves<DYN_T>();
   constexpr int NTHREADS = 64 * NWAVES;
   constexpr int PER_WAVE = 64 / REP;
-  __builtin_assume(__builtin_amdgcn_workgroup_size_x() == NTHREADS);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_y() == 1);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_z() == 1);
-  __builtin_assume(__builtin_amdgcn_workitem_id_x() < NTHREADS);
-  __builtin_assume(__builtin_amdgcn_workitem_id_y() == 0);
-  __builtin_assume(__builtin_amdgcn_workitem_id_z() == 0);
+  MPPI_ASSUME_BLOCK_SHAPE(NTHREADS, 1, 1);
 
   const RolloutArgs& args = rargs.base;
   DYN_T* dynamics = &dynamics_obj;
@@ -664,12 +660,7 @@ __global__ void __launch_bounds__(64 * (replicated_lanes<DYN_T>::value + INIT_EV
   constexpr int NS = INIT_EVAL_PIPE_SAMPLERS, NC = INIT_EVAL_PIPE_COSTS;
   constexpr int NTHREADS = 64 * (DW + NS + NC);
   constexpr int PER_WAVE = 64 / REP;
-  __builtin_assume(__builtin_amdgcn_workgroup_size_x() == NTHREADS);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_y() == 1);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_z() == 1);
-  __builtin_assume(__builtin_amdgcn_workitem_id_x() < NTHREADS);
-  __builtin_assume(__builtin_amdgcn_workitem_id_y() == 0);
-  __builtin_assume(__builtin_amdgcn_workitem_id_z() == 0);
+  MPPI_ASSUME_BLOCK_SHAPE(NTHREADS, 1, 1);
   DYN_T* dynamics = &dynamics_obj;
   COST_T* costs = &costs_obj;
   SAMPLING_T* sampling = &sampling_obj;

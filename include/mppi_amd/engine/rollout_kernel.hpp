@@ -341,12 +341,7 @@ __global__ void __launch_bounds__(BX* BY* BZ* replicated_lanes<DYN_T>::value)
   static_assert(REP == 1 || (BY == 1 && 64 % REP == 0 && (BX * REP) % 64 == 0), "replicated lanes need BY == 1 and whole waves");
   // The block shape is a template parameter; telling the compiler lets the plugins' threadIdx.y / blockDim.y loops
   // fold (see mppi_amd/plugin/parallel_utils.hpp).
-  __builtin_assume(__builtin_amdgcn_workgroup_size_x() == BX * REP);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_y() == BY);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_z() == BZ);
-  __builtin_assume(__builtin_amdgcn_workitem_id_x() < BX * REP);
-  __builtin_assume(__builtin_amdgcn_workitem_id_y() < BY);
-  __builtin_assume(__builtin_amdgcn_workitem_id_z() < BZ);
+  MPPI_ASSUME_BLOCK_SHAPE(BX * REP, BY, BZ);
 
   DYN_T* dynamics = &dynamics_obj;
   COST_T* costs = &costs_obj;

@@ -36,6 +36,7 @@
 #include "rollout_kernel.hpp"
 #include "merge_wave.hpp"
 #include "kernarg_view.hpp"
+#include "pipe_roles.hpp"
 #include "mppi_amd/plugin/dynamics.hpp"  // split_step
 
 namespace mppi
@@ -83,86 +84,6 @@ __host__ inline size_t pipelineSharedBytes(const DYN_T& dyn, const COST_T& cost,
   return n;
 }
 
-/** progress counters live in LDS: address-space-3 pointers keep the polls on ds_read instead of flat loads */
-typedef volatile __attribute__((address_space(3))) int* lds_counter_t;
-typedef int pipe_int4 __attribute__((ext_vector_type(4)));
-typedef volatile __attribute__((address_space(3))) pipe_int4* lds_counter4_t;
-
-/**
- * Blocks until *ctr >= need.  `cached` is the consumer's last observed value: the producer usually runs ahead, so most
- * calls return without touching LDS.
- */
-__device__ inline void pipeWait(lds_counter_t ctr, const int need, int& cached)
-{
-  if (cached >= need)
-    return;
-  int v = __builtin_amdgcn_readfirstlane(*ctr);
-  while (v < need)
-  {
-    __builtin_amdgcn_s_sleep(1);
-    v = __builtin_amdgcn_readfirstlane(*ctr);
-  }
-  cached = v;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ inline void pipePublish(lds_counter_t ctr, const int value, const int lane)
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  if (lane == 0)
-    *ctr = value;
-}
-/**
- * pipePublish for a producer whose data went to LDS ONLY (ring slots, LDS sample rows).  The LDS unit executes the DS
- * instructions of a wave in issue order (that order is what lgkmcnt counts), so the counter store below cannot become visible
- * before the data stores in front of it: no s_waitcnt is needed, only the compiler must keep the order.  The release fence of
- * pipePublish cost the dynamics wave of rolloutPipelineKernel an exposed LDS write round trip per trip (in-kernel timers,
- * profiles/r04_cartpole_pipe_timing*.json).  NOT for data stored to global memory (the HBM-row variants' sampler waves).
- */
-__device__ inline void pipePublishLds(lds_counter_t ctr, const int value, const int lane)
-{
-  asm volatile("" ::: "memory");
-  if (lane == 0)
-    *ctr = value;
-  asm volatile("" ::: "memory");
-}
-/* ---- A/B instrumentation (tools/pipe_timing.py; never defined in a product build): where the role waves of
- * rolloutPipelineRepKernel spend their time.  Every wave of the first PIPE_TIMING_BLOCKS blocks accumulates s_memtime ticks
- * (constant 100 MHz on gfx950: 10 ns — coarse per event, unbiased over the hundreds of events of a launch) per category. */
-#if defined(MPPI_PIPE_TIMING)
-constexpr int PIPE_TIMING_BLOCKS = 256, PIPE_TIMING_WAVES = 24, PIPE_TIMING_SLOTS = 8;
-static __device__ unsigned long long g_pipe_timing[PIPE_TIMING_BLOCKS * PIPE_TIMING_WAVES * PIPE_TIMING_SLOTS];
-struct PipeTimer
-{
-  unsigned long long acc[PIPE_TIMING_SLOTS] = {};
-  unsigned long long t0 = 0;
-  __device__ inline void start()
-  {
-    t0 = __builtin_amdgcn_s_memtime();
-  }
-  __device__ inline void stop(const int slot)
-  {
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-    acc[slot] += t1 - t0;
-    t0 = t1;
-  }
-  /** per-trip record of one wave (the dynamics wave of rolloutPipelineKernel): row 4 + kind of the block's table, entry trip */
-  __device__ inline void trip(const int block, const int kind, const int trip_idx, const int lane, const unsigned long long v) const
-  {
-    if (block < PIPE_TIMING_BLOCKS && lane == 0 && trip_idx < 4 * PIPE_TIMING_SLOTS && kind < 5)
-      g_pipe_timing[(block * PIPE_TIMING_WAVES + 4 + 4 * kind) * PIPE_TIMING_SLOTS + trip_idx] = v;
-  }
-  __device__ inline void flush(const int block, const int wave, const int lane) const
-  {
-    if (block < PIPE_TIMING_BLOCKS && wave < PIPE_TIMING_WAVES && lane == 0)
-      for (int i = 0; i < PIPE_TIMING_SLOTS; i++)
-        g_pipe_timing[(block * PIPE_TIMING_WAVES + wave) * PIPE_TIMING_SLOTS + i] = acc[i];
-  }
-};
-#define PIPE_T(x) x
-#else
-#define PIPE_T(x)
-#endif
-
 /** sampler waves of blocks that hold ONE set of role waves (BZ == 1, or the folded Tube variant): the draw (Philox rounds
  *  + two Box-Muller pairs per quad, ~320 dependent instructions) is as long as the dynamics of four cart-pole steps, and a
  *  block of three waves leaves the CU's fourth SIMD idle — a second sampler wave taking alternate trips is free */
@@ -206,12 +127,7 @@ __global__ void __launch_bounds__(pipelineBlockX(BZ, FOLD_Z) * (FOLD_Z ? 1 : BZ)
   constexpr bool PAIR_DRAW = FOLD_Z && DRAW_IN_LOOP && BZ == 2 && DYN_T::CONTROL_DIM == 2;
   constexpr int WX = pipelineBlockX(BZ, FOLD_Z);
   constexpr int NS = WX / 64 - 2;  // sampler waves
-  __builtin_assume(__builtin_amdgcn_workgroup_size_x() == WX);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_y() == 1);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_z() == WZ);
-  __builtin_assume(__builtin_amdgcn_workitem_id_x() < WX);
-  __builtin_assume(__builtin_amdgcn_workitem_id_y() == 0);
-  __builtin_assume(__builtin_amdgcn_workitem_id_z() < WZ);
+  MPPI_ASSUME_BLOCK_SHAPE(WX, 1, WZ);
 
   PIPE_T(PipeTimer tm; tm.start(); const unsigned long long t_entry = wall_clock64();)
   DYN_T* dynamics = &dynamics_obj;
@@ -838,17 +754,6 @@ __host__ inline int pipelineRepRingSteps(const DYN_T& dyn, const COST_T& cost, c
   return 0;
 }
 
-/** pins every 32-bit word of a (trivially copyable) object to a VGPR: see the cost wave of rolloutPipelineRepKernel */
-template <class T>
-__device__ inline void vgprResident(T& obj)
-{
-  static_assert(sizeof(T) % 4 == 0, "whole words");
-  uint32_t* w = reinterpret_cast<uint32_t*>(&obj);
-#pragma unroll
-  for (int i = 0; i < (int)(sizeof(T) / 4); i++)
-    asm volatile("" : "+v"(w[i]));
-}
-
 /**
  * ROWS_HBM (long horizons: T * C floats per rollout do not fit the LDS next to the ring): the block's sample rows live in the
  * sampler's HBM buffer (blockRows).  The sampler waves write them there (write-through stores, nobody waits for them), the
@@ -883,12 +788,7 @@ __global__ void MPPI_PIPE_REP_BOUNDS(64 * (replicated_lanes<DYN_T>::value + PIPE
   constexpr int NWAVES = DW + NS + NC;
   constexpr int NTHREADS = 64 * NWAVES;
   constexpr int PER_WAVE = 64 / REP;
-  __builtin_assume(__builtin_amdgcn_workgroup_size_x() == NTHREADS);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_y() == 1);
-  __builtin_assume(__builtin_amdgcn_workgroup_size_z() == 1);
-  __builtin_assume(__builtin_amdgcn_workitem_id_x() < NTHREADS);
-  __builtin_assume(__builtin_amdgcn_workitem_id_y() == 0);
-  __builtin_assume(__builtin_amdgcn_workitem_id_z() == 0);
+  MPPI_ASSUME_BLOCK_SHAPE(NTHREADS, 1, 1);
 
   DYN_T* dynamics = &dynamics_obj;
   COST_T* costs = &costs_obj;
