@@ -30,97 +30,101 @@ def build(force=False):
     return LIB
 
 
+def declare(L):
+    """the prototypes of oracle_capi.cpp's entry points, on any library that embeds it"""
+    L.oracle_create.restype = C.c_void_p
+    L.oracle_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]
+    L.oracle_destroy.argtypes = [C.c_void_p]
+    L.oracle_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
+    L.oracle_set_dynamics_params.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.oracle_set_cost_params.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.oracle_set_blob.argtypes = [C.c_void_p, C.c_char_p, _f32p, C.c_size_t, C.POINTER(C.c_int), C.c_int]
+    L.oracle_fnn_forward.argtypes = [C.POINTER(C.c_int), C.c_int, _f32p, _f32p, _f32p]
+    L.oracle_fnn_forward2.argtypes = [C.POINTER(C.c_int), C.c_int, _f32p, _f32p, _f32p, C.c_int]
+    L.oracle_lstm_forward2.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _f32p, _f32p, _f32p, C.c_int,
+                                       _f32p, C.c_int]
+    L.oracle_set_split_output_sum.argtypes = [C.c_void_p, C.c_int]
+    L.oracle_lstm_forward.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _f32p, _f32p, _f32p, C.c_int,
+                                      _f32p]
+    L.oracle_state_deriv.argtypes = [C.c_void_p, _f32p, _f32p, _f32p]
+    L.oracle_texture2d_query.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _f32p, _f32p, _f32p,
+                                         _f32p, _f32p, C.c_int, C.c_int, _f32p]
+    L.oracle_update_state.argtypes = [C.c_void_p, _f32p, _f32p, C.c_float, _f32p]
+    L.oracle_state_cost.restype = C.c_float
+    L.oracle_state_cost.argtypes = [C.c_void_p, _f32p, C.c_int, C.POINTER(C.c_int)]
+    L.oracle_ar_cost_term.restype = C.c_float
+    L.oracle_ar_cost_term.argtypes = [C.c_void_p, C.c_int, _f32p, C.POINTER(C.c_int)]
+    L.oracle_ar_coor_transform.argtypes = [C.c_void_p, C.c_float, C.c_float, _f32p]
+    L.oracle_set_colored_mppi_params.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int]
+    L.oracle_set_control_ranges.argtypes = [C.c_void_p, _f32p]
+    L.oracle_set_control_deadband.argtypes = [C.c_void_p, _f32p]
+    L.oracle_set_sampler.argtypes = [C.c_void_p, _f32p, _f32p, C.c_float, C.c_float, C.c_int]
+    L.oracle_set_independent_noise.argtypes = [C.c_void_p, C.c_int]
+    L.oracle_set_time_specific_std_dev.argtypes = [C.c_void_p, C.c_void_p]
+    L.oracle_set_controller_params.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+    L.oracle_set_gaussian_controls.argtypes = [C.c_void_p, _f32p, _f32p, C.c_int, C.c_int, _f32p]
+    L.oracle_rollout_costs.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p, C.c_int]
+    L.oracle_best_index.restype = C.c_int
+    L.oracle_best_index.argtypes = [_f32p, C.c_int]
+    L.oracle_baseline.restype = C.c_float
+    L.oracle_baseline.argtypes = [_f32p, C.c_int]
+    L.oracle_norm_exp.argtypes = [_f32p, C.c_int, C.c_float, C.c_float]
+    L.oracle_normalizer.restype = C.c_float
+    L.oracle_normalizer.argtypes = [_f32p, C.c_int]
+    L.oracle_free_energy.argtypes = [_f32p, C.c_int, C.c_float, C.c_float, _f32p]
+    L.oracle_weighted_reduction.argtypes = [_f32p, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]
+    L.oracle_smooth.argtypes = [_f32p, _f32p, C.c_int, C.c_int]
+    L.oracle_slide.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p]
+    L.oracle_save_history.argtypes = [C.c_int, _f32p, _f32p, C.c_int]
+    L.oracle_state_trajectory.argtypes = [C.c_void_p, _f32p, _f32p, _f32p]
+    L.oracle_output_trajectory.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p]
+    L.oracle_model_step.argtypes = [C.c_void_p, _f32p, _f32p, C.c_float]
+    L.oracle_enforce_leash.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p]
+    L.oracle_model_step_full.argtypes = [C.c_void_p, _f32p, _f32p, C.c_float, _f32p, _f32p, _f32p]
+    L.oracle_set_nominal_control.argtypes = [C.c_void_p, _f32p]
+    L.oracle_iterate.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p]
+    L.oracle_vanilla_compute_control.argtypes = [C.c_void_p, _f32p, C.c_int, _f32p]
+    L.oracle_tube_compute_control.argtypes = [C.c_void_p, _f32p, C.c_int, _f32p]
+    L.oracle_vanilla_slide.argtypes = [C.c_void_p, C.c_int]
+    L.oracle_tube_slide.argtypes = [C.c_void_p, C.c_int]
+    for n in ("control", "nominal_control", "state_traj", "nominal_state_traj", "costs", "weights", "samples",
+              "stats"):
+        getattr(L, "oracle_get_" + n).argtypes = [C.c_void_p, _f32p]
+    L.oracle_colored_noise.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_float, C.c_float, C.c_int,
+                                       _f32p, _f32p]
+    L.oracle_colored_weights.argtypes = [C.c_int, C.c_int, _f32p, C.c_float, _f32p, _f32p]
+    L.oracle_philox_spectrum.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]
+    L.oracle_colored_compute_control.argtypes = [C.c_void_p, _f32p, C.c_int, _f32p, _f32p, C.c_float, C.c_float]
+    _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
+    L.oracle_rmppi_create.restype = C.c_void_p
+    L.oracle_rmppi_create.argtypes = [C.c_void_p]
+    L.oracle_rmppi_destroy.argtypes = [C.c_void_p]
+    L.oracle_rmppi_set_params.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int]
+    L.oracle_rmppi_set_gains.argtypes = [C.c_void_p, _f32p, C.c_int]
+    L.oracle_rmppi_feedback.argtypes = [C.c_void_p, _f32p, _f32p, C.c_int, _f32p]
+    L.oracle_rmppi_line_search.argtypes = [C.c_void_p, C.c_int, _f32p, _i32p]
+    L.oracle_rmppi_candidates.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p]
+    L.oracle_rmppi_best_index.restype = C.c_int
+    L.oracle_rmppi_best_index.argtypes = [C.c_void_p, _f32p, _f32p]
+    L.oracle_rmppi_rollout_costs.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p]
+    L.oracle_rmppi_update_importance_sampling.argtypes = [C.c_void_p, _f32p, C.c_int, _f32p]
+    L.oracle_rmppi_compute_control.argtypes = [C.c_void_p, _f32p, C.c_int, _f32p]
+    L.oracle_rmppi_get_state.argtypes = [C.c_void_p, _f32p, _i32p, _f32p, C.c_void_p]
+    L.oracle_philox4x32_10.argtypes = [_u32p, _u32p, _u32p]
+    L.oracle_philox_normal.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, _f32p]
+    L.oracle_det_eval.argtypes = [C.c_int, _f32p, _f32p, C.c_int]
+    L.oracle_time_iterations.restype = C.c_double
+    L.oracle_time_iterations.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int]
+    L.oracle_max_threads.restype = C.c_int
+    return L
+
+
 def lib():
     global _lib
     if _lib is None:
         build()
-        L = C.CDLL(LIB)
-        L.oracle_create.restype = C.c_void_p
-        L.oracle_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]
-        L.oracle_destroy.argtypes = [C.c_void_p]
-        L.oracle_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-        L.oracle_set_dynamics_params.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.oracle_set_cost_params.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.oracle_set_blob.argtypes = [C.c_void_p, C.c_char_p, _f32p, C.c_size_t, C.POINTER(C.c_int), C.c_int]
-        L.oracle_fnn_forward.argtypes = [C.POINTER(C.c_int), C.c_int, _f32p, _f32p, _f32p]
-        L.oracle_fnn_forward2.argtypes = [C.POINTER(C.c_int), C.c_int, _f32p, _f32p, _f32p, C.c_int]
-        L.oracle_lstm_forward2.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _f32p, _f32p, _f32p, C.c_int,
-                                           _f32p, C.c_int]
-        L.oracle_set_split_output_sum.argtypes = [C.c_void_p, C.c_int]
-        L.oracle_lstm_forward.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _f32p, _f32p, _f32p, C.c_int,
-                                          _f32p]
-        L.oracle_state_deriv.argtypes = [C.c_void_p, _f32p, _f32p, _f32p]
-        L.oracle_texture2d_query.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _f32p, _f32p, _f32p,
-                                             _f32p, _f32p, C.c_int, C.c_int, _f32p]
-        L.oracle_update_state.argtypes = [C.c_void_p, _f32p, _f32p, C.c_float, _f32p]
-        L.oracle_state_cost.restype = C.c_float
-        L.oracle_state_cost.argtypes = [C.c_void_p, _f32p, C.c_int, C.POINTER(C.c_int)]
-        L.oracle_ar_cost_term.restype = C.c_float
-        L.oracle_ar_cost_term.argtypes = [C.c_void_p, C.c_int, _f32p, C.POINTER(C.c_int)]
-        L.oracle_ar_coor_transform.argtypes = [C.c_void_p, C.c_float, C.c_float, _f32p]
-        L.oracle_set_colored_mppi_params.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int]
-        L.oracle_set_control_ranges.argtypes = [C.c_void_p, _f32p]
-        L.oracle_set_control_deadband.argtypes = [C.c_void_p, _f32p]
-        L.oracle_set_sampler.argtypes = [C.c_void_p, _f32p, _f32p, C.c_float, C.c_float, C.c_int]
-        L.oracle_set_independent_noise.argtypes = [C.c_void_p, C.c_int]
-        L.oracle_set_time_specific_std_dev.argtypes = [C.c_void_p, C.c_void_p]
-        L.oracle_set_controller_params.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
-        L.oracle_set_gaussian_controls.argtypes = [C.c_void_p, _f32p, _f32p, C.c_int, C.c_int, _f32p]
-        L.oracle_rollout_costs.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p, C.c_int]
-        L.oracle_best_index.restype = C.c_int
-        L.oracle_best_index.argtypes = [_f32p, C.c_int]
-        L.oracle_baseline.restype = C.c_float
-        L.oracle_baseline.argtypes = [_f32p, C.c_int]
-        L.oracle_norm_exp.argtypes = [_f32p, C.c_int, C.c_float, C.c_float]
-        L.oracle_normalizer.restype = C.c_float
-        L.oracle_normalizer.argtypes = [_f32p, C.c_int]
-        L.oracle_free_energy.argtypes = [_f32p, C.c_int, C.c_float, C.c_float, _f32p]
-        L.oracle_weighted_reduction.argtypes = [_f32p, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]
-        L.oracle_smooth.argtypes = [_f32p, _f32p, C.c_int, C.c_int]
-        L.oracle_slide.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p]
-        L.oracle_save_history.argtypes = [C.c_int, _f32p, _f32p, C.c_int]
-        L.oracle_state_trajectory.argtypes = [C.c_void_p, _f32p, _f32p, _f32p]
-        L.oracle_output_trajectory.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p]
-        L.oracle_model_step.argtypes = [C.c_void_p, _f32p, _f32p, C.c_float]
-        L.oracle_enforce_leash.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p]
-        L.oracle_model_step_full.argtypes = [C.c_void_p, _f32p, _f32p, C.c_float, _f32p, _f32p, _f32p]
-        L.oracle_set_nominal_control.argtypes = [C.c_void_p, _f32p]
-        L.oracle_iterate.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p]
-        L.oracle_vanilla_compute_control.argtypes = [C.c_void_p, _f32p, C.c_int, _f32p]
-        L.oracle_tube_compute_control.argtypes = [C.c_void_p, _f32p, C.c_int, _f32p]
-        L.oracle_vanilla_slide.argtypes = [C.c_void_p, C.c_int]
-        L.oracle_tube_slide.argtypes = [C.c_void_p, C.c_int]
-        for n in ("control", "nominal_control", "state_traj", "nominal_state_traj", "costs", "weights", "samples",
-                  "stats"):
-            getattr(L, "oracle_get_" + n).argtypes = [C.c_void_p, _f32p]
-        L.oracle_colored_noise.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_float, C.c_float, C.c_int,
-                                           _f32p, _f32p]
-        L.oracle_colored_weights.argtypes = [C.c_int, C.c_int, _f32p, C.c_float, _f32p, _f32p]
-        L.oracle_philox_spectrum.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]
-        L.oracle_colored_compute_control.argtypes = [C.c_void_p, _f32p, C.c_int, _f32p, _f32p, C.c_float, C.c_float]
-        _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
-        L.oracle_rmppi_create.restype = C.c_void_p
-        L.oracle_rmppi_create.argtypes = [C.c_void_p]
-        L.oracle_rmppi_destroy.argtypes = [C.c_void_p]
-        L.oracle_rmppi_set_params.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int]
-        L.oracle_rmppi_set_gains.argtypes = [C.c_void_p, _f32p, C.c_int]
-        L.oracle_rmppi_feedback.argtypes = [C.c_void_p, _f32p, _f32p, C.c_int, _f32p]
-        L.oracle_rmppi_line_search.argtypes = [C.c_void_p, C.c_int, _f32p, _i32p]
-        L.oracle_rmppi_candidates.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p]
-        L.oracle_rmppi_best_index.restype = C.c_int
-        L.oracle_rmppi_best_index.argtypes = [C.c_void_p, _f32p, _f32p]
-        L.oracle_rmppi_rollout_costs.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _f32p]
-        L.oracle_rmppi_update_importance_sampling.argtypes = [C.c_void_p, _f32p, C.c_int, _f32p]
-        L.oracle_rmppi_compute_control.argtypes = [C.c_void_p, _f32p, C.c_int, _f32p]
-        L.oracle_rmppi_get_state.argtypes = [C.c_void_p, _f32p, _i32p, _f32p, C.c_void_p]
-        L.oracle_philox4x32_10.argtypes = [_u32p, _u32p, _u32p]
-        L.oracle_philox_normal.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.c_int, _f32p]
-        L.oracle_det_eval.argtypes = [C.c_int, _f32p, _f32p, C.c_int]
-        L.oracle_time_iterations.restype = C.c_double
-        L.oracle_time_iterations.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int]
-        L.oracle_max_threads.restype = C.c_int
-        _lib = L
+        _lib = declare(C.CDLL(LIB))
     return _lib
 
 

@@ -1,29 +1,24 @@
 """The CPU restatement of ARRobustCost (ar_robust_oracle.cpp) and the host build of the shipped class (robust_cost_host.hip) for
 the tests: build helpers and ctypes loaders.
 
-ar_robust_oracle.cpp is compiled together with the unchanged oracle/oracle_capi.cpp into ONE library, with the flags of
-oracle/Makefile, exactly as tests/quadrotor_map_oracle/__init__.py builds its own: the handle is an oracle::Controller (the
+ar_robust_oracle.cpp is compiled together with the unchanged oracle/oracle_capi.cpp into ONE library (tests/native_build.py:
+oracle_lib, the flags of oracle/Makefile): the handle is an oracle::Controller (the
 oracle's ARNeuralNetModel + the restated cost) and every oracle_* entry point takes it, the Robust MPPI ones included.
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import native_build as nb
 import pyoracle as po
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-ORACLE = os.path.join(REPO, "oracle")
 LIB = os.path.join(HERE, "_build", "libar_robust_oracle.so")
 HOST_LIB = os.path.join(HERE, "_build", "librobust_cost_host.so")
 MODEL_SRC = os.path.join(REPO, "examples", "autorally_robust_model", "autorally_robust_model.hip")
 MODEL_LIB = os.path.join(REPO, "examples", "_build", "libautorally_robust_model.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-# oracle/Makefile's CXXFLAGS: -ffp-contract=off keeps det::fma() the only fused operation
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-Wall",
-            "-Wno-unused-parameter"]
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _lib = _host = None
@@ -32,48 +27,21 @@ CENSUS = ("below_threshold", "on_ramp", "saturated", "track_on", "track_off", "s
           "slip_below", "slip_ramp", "slip_saturated", "rolled", "max_cost")
 
 
-def _include_files():
-    return [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(REPO, "include")) for f in fs]
-
-
-def _stale(target, deps):
-    return not os.path.exists(target) or any(os.path.getmtime(s) > os.path.getmtime(target) for s in deps)
-
-
-def _compile(cmd, target, what):
-    os.makedirs(os.path.dirname(target), exist_ok=True)
-    r = subprocess.run(cmd + ["-o", target + ".tmp"], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(what + " build failed:\n" + r.stdout[-3000:] + r.stderr[-6000:])
-    os.replace(target + ".tmp", target)
-
-
 def build():
     src = os.path.join(HERE, "ar_robust_oracle.cpp")
-    deps = [src, os.path.abspath(__file__)]
-    deps += [os.path.join(ORACLE, f) for f in os.listdir(ORACLE) if f.endswith((".cpp", ".hpp"))]
-    deps += [os.path.join(REPO, "include", "mppi_amd", f) for f in ("det_math.h", "model_params.h")]
-    if _stale(LIB, deps):
-        _compile([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I" + os.path.join(REPO, "include"), "-I" + ORACLE, "-shared",
-                 os.path.join(ORACLE, "oracle_capi.cpp"), src], LIB, "AutoRally robust oracle")
-    return LIB
+    return nb.build(LIB, nb.oracle_lib(src), [src, os.path.abspath(__file__)] + nb.oracle_files(), "AutoRally robust oracle")
 
 
 def lib():
     global _lib
     if _lib is None:
-        L = C.CDLL(build())
+        L = po.declare(C.CDLL(build()))  # the oracle's own entry points, the Robust MPPI ones included
         h = C.c_void_p
         L.ar_robust_oracle_create.restype = h
         L.ar_robust_oracle_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]
         L.ar_robust_set_costmap.argtypes = [h, _f32p, C.c_int, C.c_int]
         L.ar_robust_terms.argtypes = [h, _f32p, _f32p]
         L.ar_robust_census.argtypes = [h, _f32p, _f32p, C.c_int, C.c_int, _i32p]
-        # the library holds oracle_capi.cpp too: its entry points get the declarations oracle/pyoracle.py gives its own copy
-        for name, fn in list(vars(po.lib()).items()):
-            if name.startswith("oracle_") and getattr(fn, "argtypes", None) is not None:
-                mine = getattr(L, name)
-                mine.argtypes, mine.restype = fn.argtypes, fn.restype
         _lib = L
     return _lib
 
@@ -141,10 +109,7 @@ class HostCost:
         global _host
         if _host is None:
             src = os.path.join(HERE, "robust_cost_host.hip")
-            if _stale(HOST_LIB, [src] + _include_files()):
-                _compile([HIPCC, "--offload-arch=gfx950", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC",
-                          "-shared", "-Werror", "-I" + os.path.join(REPO, "include"), src], HOST_LIB, "robust_cost_host")
-            L = C.CDLL(HOST_LIB)
+            L = C.CDLL(nb.build(HOST_LIB, nb.hip_host_lib(src, "-Werror"), [src] + nb.include_files(), "robust_cost_host"))
             L.robust_cost_default_params.argtypes = [C.c_void_p]
             L.robust_cost_field_offsets.argtypes = [_i32p, _i32p]
             L.robust_cost_set_params.argtypes = [C.c_void_p]
@@ -192,11 +157,4 @@ class HostCost:
 def load_model(m):
     """builds examples/autorally_robust_model/autorally_robust_model.hip on its own and loads it into the engine's registry with
     mppi_load_plugin; m is the mppi_generic_amd package"""
-    lib_ = m.load_library()
-    if "autorally_nn_robust" in m.list_models():
-        return lib_
-    if _stale(MODEL_LIB, [MODEL_SRC] + _include_files()):
-        _compile([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                  "-I" + os.path.join(REPO, "include"), MODEL_SRC], MODEL_LIB, "autorally_robust_model")
-    assert lib_.mppi_load_plugin(MODEL_LIB.encode()) == m.MPPI_OK, lib_.mppi_last_error(None)
-    return lib_
+    return nb.load_plugin_model(m, "autorally_nn_robust", MODEL_SRC, MODEL_LIB)

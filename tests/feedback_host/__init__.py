@@ -1,16 +1,15 @@
 """The host build of the DDP backward pass (feedback_host.hip: include/mppi_amd/feedback_controllers/ddp_backward.hpp) for the
-tests: build helper and ctypes loader, in the pattern of tests/linearize_host: hipcc for the host alone (no device pass, nothing
+tests: ctypes loader over a library tests/native_build.py builds: hipcc for the host alone (no device pass, nothing
 of the GPU is touched when it is loaded)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import native_build as nb
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(os.path.dirname(HERE))
 HOST_LIB = os.path.join(HERE, "_build", "libfeedback_host.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _lib = None
 
@@ -19,17 +18,7 @@ def lib():
     global _lib
     if _lib is None:
         src = os.path.join(HERE, "feedback_host.hip")
-        deps = [src, os.path.join(REPO, "include", "mppi_amd", "feedback_controllers", "ddp_backward.hpp"),
-                os.path.join(REPO, "include", "mppi_amd", "det_math.h")]
-        if not os.path.exists(HOST_LIB) or any(os.path.getmtime(s) > os.path.getmtime(HOST_LIB) for s in deps):
-            os.makedirs(os.path.dirname(HOST_LIB), exist_ok=True)
-            cmd = [HIPCC, "--offload-arch=gfx950", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                   "-I" + os.path.join(REPO, "include"), src, "-o", HOST_LIB + ".tmp"]
-            r = subprocess.run(cmd, capture_output=True, text=True)
-            if r.returncode != 0:
-                raise RuntimeError("feedback_host build failed:\n" + r.stdout[-3000:] + r.stderr[-6000:])
-            os.replace(HOST_LIB + ".tmp", HOST_LIB)
-        L = C.CDLL(HOST_LIB)
+        L = C.CDLL(nb.build(HOST_LIB, nb.hip_host_lib(src), [src] + nb.include_files(), "feedback_host"))
         L.feedback_host_backward.argtypes = [C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float, C.c_int, _f32p, C.POINTER(C.c_int)]
         _lib = L
     return _lib

@@ -1,15 +1,14 @@
-"""The host build of the shipped computeGrad methods (linearize_host.hip) for the tests: build helper and ctypes loader, in the
-pattern of tests/ar_robust_oracle: hipcc for the host alone (no device pass, nothing of the GPU is touched when it is loaded)."""
+"""The host build of the shipped computeGrad methods (linearize_host.hip) for the tests: ctypes loader over a library
+tests/native_build.py builds: hipcc for the host alone (no device pass, nothing of the GPU is touched when it is loaded)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import native_build as nb
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(os.path.dirname(HERE))
 HOST_LIB = os.path.join(HERE, "_build", "liblinearize_host.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _lib = None
 
@@ -23,16 +22,7 @@ def lib():
     global _lib
     if _lib is None:
         src = os.path.join(HERE, "linearize_host.hip")
-        deps = [src] + [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(REPO, "include")) for f in fs]
-        if not os.path.exists(HOST_LIB) or any(os.path.getmtime(s) > os.path.getmtime(HOST_LIB) for s in deps):
-            os.makedirs(os.path.dirname(HOST_LIB), exist_ok=True)
-            cmd = [HIPCC, "--offload-arch=gfx950", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                   "-I" + os.path.join(REPO, "include"), src, "-o", HOST_LIB + ".tmp"]
-            r = subprocess.run(cmd, capture_output=True, text=True)
-            if r.returncode != 0:
-                raise RuntimeError("linearize_host build failed:\n" + r.stdout[-3000:] + r.stderr[-6000:])
-            os.replace(HOST_LIB + ".tmp", HOST_LIB)
-        L = C.CDLL(HOST_LIB)
+        L = C.CDLL(nb.build(HOST_LIB, nb.hip_host_lib(src), [src] + nb.include_files(), "linearize_host"))
         L.linearize_host_eval.argtypes = [C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, C.POINTER(C.c_int)]
         L.linearize_host_traits.restype = C.c_uint
         _lib = L

@@ -2,87 +2,45 @@
 (map_cost_host.hip) for the tests: build helpers and ctypes loaders.
 
 quadrotor_map_oracle.cpp includes tests/quadrotor_oracle/quadrotor_oracle.cpp (the dynamics restatement, unchanged) and is
-compiled together with the unchanged oracle/oracle_capi.cpp into ONE library, with the flags of oracle/Makefile, exactly as
-tests/quadrotor_oracle/__init__.py builds its own: the handle is an oracle::Controller and every oracle_* entry point takes it.
+compiled together with the unchanged oracle/oracle_capi.cpp into ONE library (tests/native_build.py: oracle_lib, the flags of
+oracle/Makefile): the handle is an oracle::Controller and every oracle_* entry point takes it.
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import native_build as nb
 import pyoracle as po
 import quadrotor_oracle as qo
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-ORACLE = os.path.join(REPO, "oracle")
 LIB = os.path.join(HERE, "_build", "libquadrotor_map_oracle.so")
 HOST_LIB = os.path.join(HERE, "_build", "libmap_cost_host.so")
 MODEL_SRC = os.path.join(REPO, "examples", "quadrotor_model", "quadrotor_map_model.hip")
 MODEL_LIB = os.path.join(REPO, "examples", "_build", "libquadrotor_map_model.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _lib = _host = None
 
 
-def _include_files():
-    return [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(REPO, "include")) for f in fs]
-
-
-def _stale(target, deps):
-    return not os.path.exists(target) or any(os.path.getmtime(s) > os.path.getmtime(target) for s in deps)
-
-
-def _compile(cmd, target, what):
-    os.makedirs(os.path.dirname(target), exist_ok=True)
-    r = subprocess.run(cmd + ["-o", target + ".tmp"], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(what + " build failed:\n" + r.stdout[-3000:] + r.stderr[-6000:])
-    os.replace(target + ".tmp", target)
-
-
 def build():
     src = os.path.join(HERE, "quadrotor_map_oracle.cpp")
-    deps = [src, os.path.abspath(__file__), os.path.join(qo.HERE, "quadrotor_oracle.cpp")]
-    deps += [os.path.join(ORACLE, f) for f in os.listdir(ORACLE) if f.endswith((".cpp", ".hpp"))]
-    deps += [os.path.join(REPO, "include", "mppi_amd", f) for f in ("det_math.h", "model_params.h")]
-    if _stale(LIB, deps):
-        _compile([os.environ.get("CXX", "g++")] + qo.CXXFLAGS + ["-I" + os.path.join(REPO, "include"), "-I" + ORACLE, "-shared",
-                 os.path.join(ORACLE, "oracle_capi.cpp"), src], LIB, "quadrotor map oracle")
-    return LIB
+    deps = [src, os.path.abspath(__file__), os.path.join(qo.HERE, "quadrotor_oracle.cpp")] + nb.oracle_files()
+    return nb.build(LIB, nb.oracle_lib(src), deps, "quadrotor map oracle")
 
 
 def lib():
     global _lib
     if _lib is None:
-        L = C.CDLL(build())
+        L = po.declare(C.CDLL(build()))  # the oracle's own entry points, which pyoracle.Oracle's methods call
         h = C.c_void_p
         L.quadrotor_map_oracle_create.restype = h
         L.quadrotor_map_oracle_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]
         L.quadrotor_map_set_costmap.argtypes = [h, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.quadrotor_map_terms.argtypes = [h, _f32p, _f32p]
         L.quadrotor_map_census.argtypes = [h, _f32p, _f32p, C.c_int, C.c_int, _i32p, _i32p]
-        # the oracle's own entry points the tests reach through pyoracle.Oracle's methods (oracle/pyoracle.py declares the same)
-        L.oracle_destroy.argtypes = [h]
-        L.oracle_set_dynamics_params.argtypes = [h, C.c_void_p, C.c_size_t]
-        L.oracle_set_cost_params.argtypes = [h, C.c_void_p, C.c_size_t]
-        L.oracle_state_cost.restype = C.c_float
-        L.oracle_state_cost.argtypes = [h, _f32p, C.c_int, C.POINTER(C.c_int)]
-        L.oracle_dims.argtypes = [h] + [C.POINTER(C.c_int)] * 3
-        L.oracle_set_controller_params.argtypes = [h, C.c_float, C.c_void_p]
-        L.oracle_set_control_ranges.argtypes = [h, _f32p]
-        L.oracle_set_sampler.argtypes = [h, _f32p, _f32p, C.c_float, C.c_float, C.c_int]
-        L.oracle_set_gaussian_controls.argtypes = [h, _f32p, _f32p, C.c_int, C.c_int, _f32p]
-        L.oracle_model_step.argtypes = [h, _f32p, _f32p, C.c_float]
-        L.oracle_set_nominal_control.argtypes = [h, _f32p]
-        L.oracle_vanilla_compute_control.argtypes = [h, _f32p, C.c_int, _f32p]
-        L.oracle_tube_compute_control.argtypes = [h, _f32p, C.c_int, _f32p]
-        L.oracle_vanilla_slide.argtypes = [h, C.c_int]
-        L.oracle_tube_slide.argtypes = [h, C.c_int]
-        for n in ("control", "nominal_control", "state_traj", "nominal_state_traj", "costs", "weights", "samples", "stats"):
-            getattr(L, "oracle_get_" + n).argtypes = [h, _f32p]
         _lib = L
     return _lib
 
@@ -143,10 +101,7 @@ class HostCost:
         global _host
         if _host is None:
             src = os.path.join(HERE, "map_cost_host.hip")
-            if _stale(HOST_LIB, [src] + _include_files()):
-                _compile([HIPCC, "--offload-arch=gfx950", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC",
-                          "-shared", "-Werror", "-I" + os.path.join(REPO, "include"), src], HOST_LIB, "map_cost_host")
-            L = C.CDLL(HOST_LIB)
+            L = C.CDLL(nb.build(HOST_LIB, nb.hip_host_lib(src, "-Werror"), [src] + nb.include_files(), "map_cost_host"))
             L.map_cost_default_params.argtypes = [C.c_void_p]
             L.map_cost_field_offsets.argtypes = [_i32p, _i32p]
             L.map_cost_update_waypoint.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]
@@ -192,11 +147,4 @@ class HostCost:
 def load_model(m):
     """builds examples/quadrotor_model/quadrotor_map_model.hip on its own and loads it into the engine's registry with
     mppi_load_plugin (as quadrotor_oracle.load_model does for "quadrotor"); m is the mppi_generic_amd package"""
-    lib_ = m.load_library()
-    if "quadrotor_map" in m.list_models():
-        return lib_
-    if _stale(MODEL_LIB, [MODEL_SRC] + _include_files()):
-        _compile([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                  "-I" + os.path.join(REPO, "include"), MODEL_SRC], MODEL_LIB, "quadrotor_map_model")
-    assert lib_.mppi_load_plugin(MODEL_LIB.encode()) == m.MPPI_OK, lib_.mppi_last_error(None)
-    return lib_
+    return nb.load_plugin_model(m, "quadrotor_map", MODEL_SRC, MODEL_LIB)

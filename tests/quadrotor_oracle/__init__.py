@@ -1,42 +1,28 @@
 """The CPU restatement of the quadrotor model (quadrotor_oracle.cpp) for the tests: build helper and ctypes loader.
 
 quadrotor_oracle.cpp is compiled together with the unchanged oracle/oracle_capi.cpp into ONE library
-(tests/quadrotor_oracle/_build/libquadrotor_oracle.so, with the flags of oracle/Makefile), so the handle its factory returns is
+(tests/quadrotor_oracle/_build/libquadrotor_oracle.so, by tests/native_build.py with the flags of oracle/Makefile), so the handle its factory returns is
 an oracle::Controller of that library and every oracle_* entry point takes it.  QuadrotorOracle is pyoracle.Oracle on that
-handle: the methods the tests use are declared here for this library.
+handle: pyoracle.declare gives this library the oracle's prototypes, the model's own entry points are declared here.
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import native_build as nb
 import pyoracle as po
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-ORACLE = os.path.join(REPO, "oracle")
 LIB = os.path.join(HERE, "_build", "libquadrotor_oracle.so")
-# oracle/Makefile's CXXFLAGS: -ffp-contract=off keeps det::fma() the only fused operation
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-Wall",
-            "-Wno-unused-parameter"]
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _lib = None
 
 
-def build(force=False):
-    srcs = [os.path.join(HERE, "quadrotor_oracle.cpp"), os.path.abspath(__file__)]
-    srcs += [os.path.join(ORACLE, f) for f in os.listdir(ORACLE) if f.endswith((".cpp", ".hpp"))]
-    srcs += [os.path.join(REPO, "include", "mppi_amd", f) for f in ("det_math.h", "model_params.h")]
-    if force or not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in srcs):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        cmd = [os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I" + os.path.join(REPO, "include"), "-I" + ORACLE, "-shared",
-               os.path.join(ORACLE, "oracle_capi.cpp"), os.path.join(HERE, "quadrotor_oracle.cpp"), "-o", LIB + ".tmp"]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("quadrotor oracle build failed:\n" + r.stdout + r.stderr)
-        os.replace(LIB + ".tmp", LIB)
-    return LIB
+def build():
+    src = os.path.join(HERE, "quadrotor_oracle.cpp")
+    return nb.build(LIB, nb.oracle_lib(src), [src, os.path.abspath(__file__)] + nb.oracle_files(), "quadrotor oracle")
 
 
 PLUGIN_MATH = os.path.join(HERE, "_build", "libplugin_math_host.so")
@@ -49,16 +35,7 @@ def plugin_math():
     global _plugin_math
     if _plugin_math is None:
         src = os.path.join(HERE, "plugin_math_host.hip")
-        deps = [src] + [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(REPO, "include")) for f in fs]
-        if not os.path.exists(PLUGIN_MATH) or any(os.path.getmtime(s) > os.path.getmtime(PLUGIN_MATH) for s in deps):
-            os.makedirs(os.path.dirname(PLUGIN_MATH), exist_ok=True)
-            cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "--cuda-host-only", "-O2", "-std=c++17",
-                   "-ffp-contract=off", "-fPIC", "-shared", "-I" + os.path.join(REPO, "include"), src, "-o", PLUGIN_MATH + ".tmp"]
-            r = subprocess.run(cmd, capture_output=True, text=True)
-            if r.returncode != 0:
-                raise RuntimeError("plugin_math_host build failed:\n" + r.stdout + r.stderr)
-            os.replace(PLUGIN_MATH + ".tmp", PLUGIN_MATH)
-        L = C.CDLL(PLUGIN_MATH)
+        L = C.CDLL(nb.build(PLUGIN_MATH, nb.hip_host_lib(src), [src] + nb.include_files(), "plugin_math_host"))
         L.plugin_quat_eval.argtypes = [C.c_int, _f32p, _f32p]
         L.plugin_gravity.restype = C.c_float
         L.plugin_default_params.argtypes = [C.c_void_p, C.c_void_p]
@@ -71,7 +48,7 @@ def plugin_math():
 def lib():
     global _lib
     if _lib is None:
-        L = C.CDLL(build())
+        L = po.declare(C.CDLL(build()))  # the oracle's own entry points, which pyoracle.Oracle's methods call
         h = C.c_void_p
         L.quadrotor_oracle_create.restype = h
         L.quadrotor_oracle_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]
@@ -79,35 +56,6 @@ def lib():
         L.quadrotor_terminal_cost.argtypes = [h, _f32p]
         L.quadrotor_det_atan2.argtypes = [_f32p, _f32p, _f32p, C.c_int]
         L.quadrotor_quat_eval.argtypes = [C.c_int, _f32p, _f32p]
-        # the oracle's own entry points the tests reach through pyoracle.Oracle's methods (oracle/pyoracle.py declares the same)
-        L.oracle_destroy.argtypes = [h]
-        L.oracle_dims.argtypes = [h] + [C.POINTER(C.c_int)] * 3
-        L.oracle_set_dynamics_params.argtypes = [h, C.c_void_p, C.c_size_t]
-        L.oracle_set_cost_params.argtypes = [h, C.c_void_p, C.c_size_t]
-        L.oracle_state_deriv.argtypes = [h, _f32p, _f32p, _f32p]
-        L.oracle_update_state.argtypes = [h, _f32p, _f32p, C.c_float, _f32p]
-        L.oracle_state_cost.restype = C.c_float
-        L.oracle_state_cost.argtypes = [h, _f32p, C.c_int, C.POINTER(C.c_int)]
-        L.oracle_set_control_ranges.argtypes = [h, _f32p]
-        L.oracle_set_control_deadband.argtypes = [h, _f32p]
-        L.oracle_set_sampler.argtypes = [h, _f32p, _f32p, C.c_float, C.c_float, C.c_int]
-        L.oracle_set_independent_noise.argtypes = [h, C.c_int]
-        L.oracle_set_time_specific_std_dev.argtypes = [h, C.c_void_p]
-        L.oracle_set_controller_params.argtypes = [h, C.c_float, C.c_void_p]
-        L.oracle_set_gaussian_controls.argtypes = [h, _f32p, _f32p, C.c_int, C.c_int, _f32p]
-        L.oracle_rollout_costs.argtypes = [h, _f32p, _f32p, _f32p, _f32p, C.c_int]
-        L.oracle_iterate.argtypes = [h, _f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p]
-        L.oracle_state_trajectory.argtypes = [h, _f32p, _f32p, _f32p]
-        L.oracle_output_trajectory.argtypes = [h, _f32p, _f32p, _f32p, _f32p]
-        L.oracle_model_step.argtypes = [h, _f32p, _f32p, C.c_float]
-        L.oracle_model_step_full.argtypes = [h, _f32p, _f32p, C.c_float, _f32p, _f32p, _f32p]
-        L.oracle_set_nominal_control.argtypes = [h, _f32p]
-        L.oracle_vanilla_compute_control.argtypes = [h, _f32p, C.c_int, _f32p]
-        L.oracle_tube_compute_control.argtypes = [h, _f32p, C.c_int, _f32p]
-        L.oracle_vanilla_slide.argtypes = [h, C.c_int]
-        L.oracle_tube_slide.argtypes = [h, C.c_int]
-        for n in ("control", "nominal_control", "state_traj", "nominal_state_traj", "costs", "weights", "samples", "stats"):
-            getattr(L, "oracle_get_" + n).argtypes = [h, _f32p]
         _lib = L
     return _lib
 
@@ -180,18 +128,6 @@ MODEL_LIB = os.path.join(REPO, "examples", "_build", "libquadrotor_model.so")
 
 
 def load_model(m):
-    """builds examples/quadrotor_model/quadrotor_model.hip on its own (as tests/test_plugin_model.py builds the pendulum) and
-    loads it into the engine's registry with mppi_load_plugin; m is the mppi_generic_amd package"""
-    lib_ = m.load_library()
-    if "quadrotor" in m.list_models():
-        return lib_
-    deps = [MODEL_SRC] + [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(REPO, "include")) for f in fs]
-    if not os.path.exists(MODEL_LIB) or any(os.path.getmtime(s) > os.path.getmtime(MODEL_LIB) for s in deps):
-        os.makedirs(os.path.dirname(MODEL_LIB), exist_ok=True)
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-               "-I" + os.path.join(REPO, "include"), MODEL_SRC, "-o", MODEL_LIB + ".tmp"]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        os.replace(MODEL_LIB + ".tmp", MODEL_LIB)
-    assert lib_.mppi_load_plugin(MODEL_LIB.encode()) == m.MPPI_OK, lib_.mppi_last_error(None)
-    return lib_
+    """builds examples/quadrotor_model/quadrotor_model.hip on its own and loads it into the engine's registry with
+    mppi_load_plugin; m is the mppi_generic_amd package"""
+    return nb.load_plugin_model(m, "quadrotor", MODEL_SRC, MODEL_LIB)

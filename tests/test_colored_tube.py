@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 import pyoracle as po
 from common import SEED, U_TOL, cartpole_cfg_lr, colored_cartpole, di_cfg, host_noise, host_spectrum, make_engine, make_oracle, ulp_diff
 from kernel_forms import env_override
@@ -31,7 +32,6 @@ from kernel_forms import env_override
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(REPO, "examples", "_build")
 COLORED = m.MPPI_SAMPLER_COLORED
 MODELS = ("double_integrator", "cartpole")
 DRIFT = {"double_integrator": np.array([0.05, -0.03, 0.2, -0.1], np.float32), "cartpole": np.array([0.2, -0.4, 0.1, 0.5], np.float32)}
@@ -304,21 +304,7 @@ NAME = "templated_double_integrator_colored_tube"
 
 
 def _build_example():
-    os.makedirs(OUT, exist_ok=True)
-    m.load_library()
-    src, exe = os.path.join(REPO, "examples", NAME + ".hip"), os.path.join(OUT, NAME)
-    deps = [src, m.library_path()]
-    for d, _, files in os.walk(os.path.join(REPO, "include")):
-        deps += [os.path.join(d, f) for f in files]
-    if os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(p) for p in deps):
-        return exe
-    lib_dir = os.path.dirname(m.library_path())
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Werror",
-           "-I" + os.path.join(REPO, "include"), "-I" + os.path.join(REPO, "examples"), src, "-L" + lib_dir, "-lmppi_amd",
-           "-Wl,-rpath," + lib_dir, "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    return exe
+    return nb.build_example(m, NAME, "-I" + os.path.join(REPO, "examples"))
 
 
 def test_templated_example_prints_the_sums_python_gets(gpu):

@@ -14,18 +14,14 @@ the prologue GEMM (2 buffers x 4 k-steps x 4 time blocks x 64 lanes x 4 B).  Eve
   The same stub with the Gaussian or the NLN sampler folds as before: (32, 1, 2), 8192 + 4096 + 64 * 8 * 2 * 4 = 16384.
 """
 import ctypes as C
-import os
 import subprocess
 
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 from mppi_generic_amd import capi
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(REPO, "examples", "_build")
-SRC = os.path.join(REPO, "tests", "probes", "launch_plan_sampler_probe.cpp")
-HDR = os.path.join(REPO, "mppi-generic_amd", "csrc", "launch_plan.hpp")
 
 VANILLA, TUBE, ROBUST, COLORED = 0, 1, 2, 3
 AUTO, FUSED, PIPELINE = 0, 1, 2
@@ -137,17 +133,7 @@ INDEP = [
 
 
 def _build(sanitize):
-    os.makedirs(OUT, exist_ok=True)
-    exe = os.path.join(OUT, "launch_plan_sampler_probe" + ("_asan" if sanitize else ""))
-    deps = [SRC, HDR] + [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(REPO, "include")) for f in fs]
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(p) for p in deps):
-        cmd = ["/opt/rocm/bin/hipcc", "--cuda-host-only", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(REPO, "include"),
-               "-I" + os.path.dirname(HDR), SRC, "-o", exe + ".tmp"]
-        cmd += ["-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        os.replace(exe + ".tmp", exe)
-    return exe
+    return nb.build_plan_probe("launch_plan_sampler_probe", sanitize)
 
 
 def _run(exe):

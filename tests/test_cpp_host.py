@@ -6,6 +6,7 @@ import subprocess
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(REPO, "examples", "_build", "cartpole_example")
@@ -13,15 +14,8 @@ EXE = os.path.join(REPO, "examples", "_build", "cartpole_example")
 
 def _build(name="cartpole_example"):
     m.load_library()
-    exe = os.path.join(os.path.dirname(EXE), name)
-    os.makedirs(os.path.dirname(EXE), exist_ok=True)
-    lib_dir = os.path.dirname(m.library_path())
-    cmd = ["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-pthread", "-I" + os.path.join(REPO, "include"),
-           os.path.join(REPO, "examples", name + ".cpp"), "-L" + lib_dir, "-lmppi_amd",
-           "-Wl,-rpath," + lib_dir, "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    src = os.path.join(REPO, "examples", name + ".cpp")
+    return nb.build(os.path.join(os.path.dirname(EXE), name), nb.abi_client(m, src), [src] + nb.library_deps(m), name)
 
 
 def test_cpp_host_example_builds_and_fails_loudly_without_device(lib):

@@ -2,20 +2,19 @@
 the host build of the same header (tests/feedback_host), bit for bit; the trajectory entry against the points entry; the in-place
 install on a Robust handle against an upload; the refusals; non-interference with computeControl; the C++ surfaces.  The host
 build itself is held to float64 in tests/test_feedback.py."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 import feedback_host as fh
 import linearize_cases as lc
 import linearize_host as lh
 from common import SEED, cartpole_cfg, di_cfg, host_noise, make_engine, rm_cfg
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BLOB, _ = lc.autorally_weights()
 DT = 0.02
 ACCEPTANCE_Q = np.diag([500.0, 500.0, 100.0, 100.0]).astype(np.float32)
@@ -272,29 +271,10 @@ def _serial_sum(G):
     return total
 
 
-def _stale(exe, src):
-    deps = [src, m.library_path()] + [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(REPO, "include")) for f in fs]
-    return not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(p) for p in deps)
-
-
 def _build_program(name):
     """compute_feedback_host.cpp with g++ over the C ABI; compute_feedback_templated.hip with hipcc, its kernels instantiated in
-    the program's own translation unit (as tests/test_linearize_gpu.py builds its programs)"""
-    m.load_library()
-    src = os.path.join(REPO, "tests", "probes", name)
-    exe = os.path.join(REPO, "examples", "_build", os.path.splitext(name)[0])
-    if _stale(exe, src):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        lib_dir = os.path.dirname(m.library_path())
-        tail = ["-I" + os.path.join(REPO, "include"), src, "-L" + lib_dir, "-lmppi_amd", "-Wl,-rpath," + lib_dir, "-o", exe + ".tmp"]
-        if name.endswith(".hip"):
-            cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Werror"] + tail
-        else:
-            cmd = ["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-pthread"] + tail
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
-        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-        os.replace(exe + ".tmp", exe)
-    return exe
+    the program's own translation unit (tests/native_build.py: build_probe_program)"""
+    return nb.build_probe_program(m, name)
 
 
 POINTS_X = np.array([[0.3, -0.4, 0.7, 1.5], [-1.0, 0.2, 2.9, -2.0]], np.float32)

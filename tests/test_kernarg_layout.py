@@ -10,6 +10,8 @@ import subprocess
 
 import pytest
 
+import native_build as nb
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(REPO, "examples", "_build")
 SRC = os.path.join(REPO, "tests", "probes", "kernarg_layout_probe.hip")
@@ -17,16 +19,12 @@ LLVM = "/opt/rocm/lib/llvm/bin/"
 
 
 def _build():
-    os.makedirs(OUT, exist_ok=True)
-    exe, co = os.path.join(OUT, "kernarg_layout_probe"), os.path.join(OUT, "kernarg_layout_probe.co")
-    hdr = os.path.join(REPO, "include", "mppi_amd", "engine", "kernarg_view.hpp")
-    if not (os.path.exists(exe) and os.path.exists(co) and
-            os.path.getmtime(exe) >= max(os.path.getmtime(SRC), os.path.getmtime(hdr))):
-        common = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(REPO, "include"), SRC]
-        for cmd in (common + ["--cuda-device-only", "--no-gpu-bundle-output", "-c", "-o", co], common + ["-o", exe]):
-            r = subprocess.run(cmd, capture_output=True, text=True)
-            assert r.returncode == 0, r.stderr[-3000:]
-    return exe, co
+    """(the probe program, the device code object alone): two targets of one source"""
+    common = [nb.hipcc(), nb.ARCH, "-O3", "-std=c++17", "-I" + nb.INCLUDE, SRC]
+    deps = [SRC] + nb.include_files()
+    return (nb.build(os.path.join(OUT, "kernarg_layout_probe"), common, deps, "kernarg_layout_probe"),
+            nb.build(os.path.join(OUT, "kernarg_layout_probe.co"), common + ["--cuda-device-only", "--no-gpu-bundle-output", "-c"], deps,
+                     "kernarg_layout_probe.co"))
 
 
 def test_kernarg_layout_formula_matches_the_compilers_metadata():

@@ -19,13 +19,13 @@ prints them):
     autorally_nn        8.80e-07                            3.52e-06       1.25e-06
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import linearize_cases as lc
 import linearize_host as lh
+import native_build as nb
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = 9.81
@@ -342,8 +342,7 @@ def test_reference_style_example_still_compiles():
     with open(probe, "w") as f:
         f.write('#include "my_model/pendulum_model_reference_style.hip"\n'
                 'static_assert(!mppi::has_compute_grad<RefPendulumDynamics>::value, "");\n')
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(REPO, "include"),
-                        "-I" + os.path.join(REPO, "examples"), probe], capture_output=True, text=True)
+    r = nb.hip_syntax_only(probe, "-I" + os.path.join(REPO, "examples"))
     assert r.returncode == 0, r.stderr[-3000:]
 
 
@@ -361,6 +360,5 @@ def test_templated_controller_accessor_compiles():
                 '  CartpoleMPPI::state_array x = CartpoleMPPI::state_array::Zero();\n'
                 '  CartpoleMPPI::control_array u = CartpoleMPPI::control_array::Zero();\n'
                 '  float a[16], b[4];\n  c.computeGradTrajectory(A, B);\n  return c.computeGrad(x, u, a, b);\n}\n')
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(REPO, "include"),
-                        probe], capture_output=True, text=True)
+    r = nb.hip_syntax_only(probe)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,19 +1,18 @@
 """mppi_linearize / mppi_linearize_trajectory on the device (engine/linearize_kernel.hpp) against the host build of the same
 model headers (tests/linearize_host), bit for bit; the refusals; non-interference with computeControl; the Python and C++
 surfaces.  The host build itself is held to float64 in tests/test_linearize.py."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 import linearize_cases as lc
 import linearize_host as lh
 from common import SEED, cartpole_cfg, di_cfg, host_noise, make_engine
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BLOB, _ = lc.autorally_weights()
 # one lane / one wave; a last block one point short; full blocks only; a tail block of one point (blocks of 64 points for the
 # lane-per-point models, of 16 for the network model)
@@ -193,29 +192,10 @@ def _serial_sum(A, B):
     return total
 
 
-def _stale(exe, src):
-    deps = [src, m.library_path()] + [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(REPO, "include")) for f in fs]
-    return not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(p) for p in deps)
-
-
 def _build_program(name):
     """compute_grad_host.cpp with g++ over the C ABI; compute_grad_templated.hip with hipcc, its kernels instantiated in the
-    program's own translation unit (as tests/test_templated_controllers.py builds the templated examples)"""
-    m.load_library()
-    src = os.path.join(REPO, "tests", "probes", name)
-    exe = os.path.join(REPO, "examples", "_build", os.path.splitext(name)[0])
-    if _stale(exe, src):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        lib_dir = os.path.dirname(m.library_path())
-        tail = ["-I" + os.path.join(REPO, "include"), src, "-L" + lib_dir, "-lmppi_amd", "-Wl,-rpath," + lib_dir, "-o", exe + ".tmp"]
-        if name.endswith(".hip"):
-            cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Werror"] + tail
-        else:
-            cmd = ["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-pthread"] + tail
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
-        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-        os.replace(exe + ".tmp", exe)
-    return exe
+    program's own translation unit (tests/native_build.py: build_probe_program)"""
+    return nb.build_probe_program(m, name)
 
 
 @pytest.fixture(scope="module")

@@ -6,21 +6,16 @@ import subprocess
 
 import pytest
 
+import native_build as nb
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(REPO, "examples", "_build", "parallel_index_probe")
 
 
 def _build():
-    os.makedirs(os.path.dirname(EXE), exist_ok=True)
     src = os.path.join(REPO, "tests", "probes", "parallel_index_probe.hip")
-    hdr = os.path.join(REPO, "include", "mppi_amd", "plugin", "parallel_utils.hpp")
-    if os.path.exists(EXE) and os.path.getmtime(EXE) > max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        return EXE
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O2", "-std=c++17",
-           "-I" + os.path.join(REPO, "include"), src, "-o", EXE]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return EXE
+    return nb.build(EXE, [nb.hipcc(), nb.ARCH, "-O2", "-std=c++17", "-I" + nb.INCLUDE, src], [src] + nb.include_files(),
+                    "parallel_index_probe")
 
 
 def test_parallel_probe_builds():

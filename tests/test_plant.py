@@ -251,16 +251,10 @@ def test_buffered_plant_history_and_lstm_hook():
 
 def test_cpp_buffered_plant_probe(lib):
     """the same on the C++ class (include/mppi_amd/plant.hpp: mppi_amd::BufferedPlant) with a stub controller: g++ only, no device"""
-    import os
     import subprocess
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(repo, "examples", "_build", "buffered_plant_probe")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    lib_dir = os.path.dirname(m.library_path())
-    r = subprocess.run(["g++", "-std=c++11", "-O1", "-Wall", "-Werror", "-pthread", "-I" + os.path.join(repo, "include"),
-                        os.path.join(repo, "tests", "probes", "buffered_plant_probe.cpp"), "-L" + lib_dir, "-lmppi_amd",
-                        "-Wl,-rpath," + lib_dir, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+
+    import native_build as nb
+    exe = nb.build_probe_program(m, "buffered_plant_probe.cpp", opt="-O1")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "BUFFERED PLANT OK" in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 from common import SEED, host_noise
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,26 +33,16 @@ SRC_REF_STYLE = os.path.join(REPO, "examples", "my_model", "pendulum_model_refer
 PLUGIN_REF_STYLE = os.path.join(OUT_DIR, "libpendulum_model_reference_style.so")
 
 
-def build_plugin(src=SRC, out=PLUGIN):
-    newest = max(os.path.getmtime(src), os.path.getmtime(os.path.join(REPO, "examples", "my_model", "pendulum_reference_style.cuh")))
-    for d, _, files in os.walk(os.path.join(REPO, "include")):
-        for f in files:
-            newest = max(newest, os.path.getmtime(os.path.join(d, f)))
-    if os.path.exists(out) and os.path.getmtime(out) >= newest:
-        return out
-    os.makedirs(OUT_DIR, exist_ok=True)
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-           "-I" + os.path.join(REPO, "include"), src, "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return out
+REF_STYLE_HDR = [os.path.join(REPO, "examples", "my_model", "pendulum_reference_style.cuh")]
+
+
+def build_plugin(src, out):
+    return nb.build_plugin(src, out, REF_STYLE_HDR)
 
 
 @pytest.fixture(scope="module")
 def plugin():
-    lib = m.load_library()
-    assert lib.mppi_load_plugin(build_plugin().encode()) == m.MPPI_OK, lib.mppi_last_error(None)
-    return lib
+    return nb.load_plugin_model(m, "user_pendulum", SRC, PLUGIN, REF_STYLE_HDR)
 
 
 def test_plugin_builds_alone_and_registers(plugin):
@@ -129,8 +120,7 @@ static_assert(!mppi_amd::templated::rolePipelineAllowed<RefPendulumDynamics, Ref
 static_assert(!mppi_amd::templated::rolePipelineAllowed<CartpoleDynamics, RefPendulumCost, G>(), "one undeclared plugin is enough");
 int main() { return 0; }
 """)
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(REPO, "include"),
-                        "-I" + os.path.join(REPO, "examples"), probe], capture_output=True, text=True)
+    r = nb.hip_syntax_only(probe, "-I" + os.path.join(REPO, "examples"))
     assert r.returncode == 0, r.stderr[-3000:]
 
 

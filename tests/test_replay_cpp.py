@@ -8,19 +8,15 @@ import subprocess
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
 def test_templated_sampled_trajectories_equal_the_c_abi(gpu, tmp_path):
-    lib_dir = os.path.dirname(m.library_path())
-    exe = str(tmp_path / "sampled_trajectories_templated")
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Werror",
-                        "-I" + os.path.join(REPO, "include"),
-                        os.path.join(REPO, "tests", "probes", "sampled_trajectories_templated.hip"), "-L" + lib_dir, "-lmppi_amd",
-                        "-Wl,-rpath," + lib_dir, "-o", exe], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
+    src = os.path.join(REPO, "tests", "probes", "sampled_trajectories_templated.hip")
+    exe = nb.build(tmp_path / "sampled_trajectories_templated", nb.hip_exe(m, src), [src], "sampled_trajectories_templated")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     mt = re.search(r"class (-?\d+) (\S+) abi (-?\d+) (\S+) scan (-?\d+) (\S+)", r.stdout)

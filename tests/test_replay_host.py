@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 from common import cartpole_cfg_lr, di_cfg, host_noise, make_oracle, ulp_diff
 from replay_cases import boundary_rows, fold_step_costs, oracle_row, selection_reference
 
@@ -86,11 +87,9 @@ def test_sampled_trajectory_list():
 def test_host_checks_under_the_sanitizers(tmp_path):
     """the index validation and the C++ list builder (include/mppi_amd/engine/replay_host.hpp) in a stand-alone program built
     with the address and undefined-behaviour sanitizers"""
-    exe = str(tmp_path / "replay_host_probe")
     src = os.path.join(REPO, "tests", "probes", "replay_host_probe.cpp")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-I" + os.path.join(REPO, "include"), src, "-o", exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = nb.build(tmp_path / "replay_host_probe", [nb.cxx(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                                                     "-fno-sanitize-recover=all", "-I" + nb.INCLUDE, src], [src], "replay_host_probe")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert "replay host checks ok" in r.stdout

@@ -13,16 +13,15 @@ iteration (tests/test_kernel_sequence.py), so the oracle is handed the mean the 
 twin handle after two iterations, which is bit for bit the mean the sampler waves merge for themselves — and the third
 generation of the Philox stream; its costs are then the handle's costs exactly, and its u* the handle's within 1e-5.
 """
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import native_build as nb
 from common import PHILOX_SEED, U_TOL, ulp_diff
 from restate64 import bits
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 EXP_LO, EXP_HI = 127 - 60, 127 + 59   # merge_wave.hpp: MERGE_Q_EXP_LO / MERGE_Q_EXP_HI — the program checks them against the header
 RANDOM_PAIRS = 1 << 24
@@ -155,10 +154,7 @@ def test_quotient_helper_arithmetic_equals_division_on_the_host(tmp_path):
     src, exe, data = tmp_path / "quotient.hip", tmp_path / "quotient", tmp_path / "pairs.f32"
     src.write_text(QUOTIENT_PROGRAM)
     np.stack([p, q], axis=1).tofile(data)
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O2", "-std=c++17",
-                        "-ffp-contract=off", "-I" + os.path.join(REPO, "include"), str(src), "-o", str(exe)],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
+    nb.build(exe, nb.hip_host(src), [src], "quotient")
     r = subprocess.run([str(exe), str(data), str(EXP_LO), str(EXP_HI)], capture_output=True, text=True, timeout=600)
     print(r.stdout[-2000:])
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]

@@ -14,6 +14,8 @@ import sys
 import numpy as np
 import pytest
 
+import native_build as nb
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # what the split leaves on the headline kernel's dynamics wave (tools/isa_step_count.py; 89.62 before it)
@@ -44,8 +46,7 @@ int main() { return 0; }
 def test_split_capability_binds_to_the_most_derived_class(tmp_path):
     src = tmp_path / "split_trait.hip"
     src.write_text(TRAIT_TU)
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only",
-                        "-I" + os.path.join(REPO, "include"), str(src)], capture_output=True, text=True, timeout=600)
+    r = nb.hip_syntax_only(src)
     assert r.returncode == 0, r.stderr[-4000:]
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 from common import cartpole_cfg, make_engine
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,20 +21,9 @@ OUT = os.path.join(REPO, "examples", "_build")
 NAMES = ("templated_cartpole", "templated_double_integrator", "templated_pendulum_reference_style")
 
 
-def _cmd(name, exe):
-    lib_dir = os.path.dirname(m.library_path())
-    return ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Werror",
-            "-I" + os.path.join(REPO, "include"), "-I" + os.path.join(REPO, "examples"),
-            os.path.join(REPO, "examples", name + ".hip"), "-L" + lib_dir, "-lmppi_amd",
-            "-Wl,-rpath," + lib_dir, "-o", exe]
-
-
-def _fresh(name):
-    src, exe = os.path.join(REPO, "examples", name + ".hip"), os.path.join(OUT, name)
-    deps = [src, m.library_path(), os.path.join(REPO, "examples", "my_model", "pendulum_reference_style.cuh")]
-    for d, _, files in os.walk(os.path.join(REPO, "include")):
-        deps += [os.path.join(d, f) for f in files]
-    return os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(p) for p in deps)
+def _job(name):
+    return nb.example_job(m, name, "-I" + os.path.join(REPO, "examples"),
+                          deps=[os.path.join(REPO, "examples", "my_model", "pendulum_reference_style.cuh")])
 
 
 # templated_double_integrator (Vanilla + Tube + Robust controllers in one unit) is a three-minute hipcc run: when this module is
@@ -44,14 +34,10 @@ _BACKGROUND = {}
 def _start_background_builds():
     try:
         from mppi_generic_amd import buildlib
-        if not os.path.exists("/opt/rocm/bin/hipcc") or buildlib.needs_build():
+        if not os.path.exists(nb.hipcc()) or buildlib.needs_build():
             return
-        os.makedirs(OUT, exist_ok=True)
         for name in NAMES:
-            if not _fresh(name):
-                tmp = os.path.join(OUT, name + ".building")
-                log = open(tmp + ".log", "w")
-                _BACKGROUND[name] = (subprocess.Popen(_cmd(name, tmp), stdout=log, stderr=subprocess.STDOUT), tmp, log)
+            _BACKGROUND[name] = nb.start(*_job(name))
     except Exception:  # noqa: BLE001 — the tests build in the foreground then
         _BACKGROUND.clear()
 
@@ -61,22 +47,8 @@ _start_background_builds()
 
 def _build(name):
     """hipcc cross-compiles the user's translation unit for gfx950 (the kernels of ITS plugin types) without a GPU"""
-    os.makedirs(OUT, exist_ok=True)
     m.load_library()
-    exe = os.path.join(OUT, name)
-    if name in _BACKGROUND:
-        proc, tmp, log = _BACKGROUND.pop(name)
-        rc = proc.wait(timeout=1200)
-        log.close()
-        assert rc == 0, open(tmp + ".log").read()[-8000:]
-        os.replace(tmp, exe)
-        os.remove(tmp + ".log")
-        return exe
-    if _fresh(name):
-        return exe
-    r = subprocess.run(_cmd(name, exe), capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    return exe
+    return nb.finish(_BACKGROUND.pop(name, None) or nb.start(*_job(name)))
 
 
 def test_reference_shaped_callers_compile():

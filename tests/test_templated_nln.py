@@ -1,7 +1,7 @@
 """NLNDistribution through the reference's TEMPLATED host surface: examples/templated_cartpole_nln.hip instantiates
 VanillaMPPIController<CartpoleDynamics, CartpoleQuadraticCost, DDPFeedback, T, K, NLNDistribution<...>> from the reference's
 include paths (<mppi/sampling_distributions/nln/nln.cuh>), which registers the instantiation under MPPI_SAMPLER_NLN and creates
-its handle with that sampler.  Built the way tests/test_templated_controllers.py builds its examples; the control sequence of
+its handle with that sampler.  Built by tests/native_build.py, as every templated example is; the control sequence of
 its first computeControl is held to the oracle fed the host-composed NLN noise of the same seed (tests/test_nln_sampler.py)."""
 import os
 import re
@@ -11,31 +11,17 @@ import numpy as np
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 import pyoracle as po
 from common import U_TOL, cartpole_cfg, make_oracle
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(REPO, "examples", "_build")
 NAME = "templated_cartpole_nln"
 K, T, SIGMA, SEED = 1024, 30, 0.8, 42  # the example's ROLLOUTS, HORIZON, std_dev and the templated controllers' default seed
 
 
 def _build():
-    os.makedirs(OUT, exist_ok=True)
-    m.load_library()
-    src, exe = os.path.join(REPO, "examples", NAME + ".hip"), os.path.join(OUT, NAME)
-    deps = [src, m.library_path()]
-    for d, _, files in os.walk(os.path.join(REPO, "include")):
-        deps += [os.path.join(d, f) for f in files]
-    if os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(p) for p in deps):
-        return exe
-    lib_dir = os.path.dirname(m.library_path())
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Werror",
-           "-I" + os.path.join(REPO, "include"), "-I" + os.path.join(REPO, "examples"), src, "-L" + lib_dir, "-lmppi_amd",
-           "-Wl,-rpath," + lib_dir, "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    return exe
+    return nb.build_example(m, NAME, "-I" + os.path.join(REPO, "examples"))
 
 
 def test_templated_nln_example_compiles_from_the_reference_include_paths():

@@ -9,11 +9,11 @@ import numpy as np
 import pytest
 
 import mppi_generic_amd as m
+import native_build as nb
 import pyoracle as po
 import quadrotor_map_oracle as qm
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(REPO, "examples", "_build")
 NAME = "templated_quadrotor_map"
 
 # the example's literals
@@ -77,16 +77,7 @@ def test_course_on_the_restatement():
 
 @pytest.fixture(scope="module")
 def exe(lib):
-    src, out = os.path.join(REPO, "examples", NAME + ".hip"), os.path.join(OUT, NAME)
-    deps = [src, m.library_path()] + [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(REPO, "include")) for f in fs]
-    if not (os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(p) for p in deps)):
-        os.makedirs(OUT, exist_ok=True)
-        lib_dir = os.path.dirname(m.library_path())
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Werror",
-               "-I" + os.path.join(REPO, "include"), src, "-L" + lib_dir, "-lmppi_amd", "-Wl,-rpath," + lib_dir, "-o", out]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=1800)
-        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    return out
+    return nb.build_example(m, NAME)
 
 
 def test_example_uses_the_reference_spellings_and_builds(exe):
