@@ -33,9 +33,10 @@ extern "C" {
 #endif
 
 #define MPPI_AMD_VERSION_MAJOR 0
-#define MPPI_AMD_VERSION_MINOR 6 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory; 4: mppi_set_feedback_params,
+#define MPPI_AMD_VERSION_MINOR 7 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory; 4: mppi_set_feedback_params,
                                     mppi_compute_feedback, mppi_compute_feedback_at; 5: mppi_create_with_sampler takes
-                                    MPPI_CONTROLLER_TUBE with MPPI_SAMPLER_COLORED; 6: mppi_top_rollouts, mppi_replay_rollouts */
+                                    MPPI_CONTROLLER_TUBE with MPPI_SAMPLER_COLORED; 6: mppi_top_rollouts, mppi_replay_rollouts;
+                                    7: mppi_evaluate_controls, mppi_warm_start */
 
 typedef struct mppi_handle_s* mppi_handle;
 
@@ -485,6 +486,43 @@ mppi_status mppi_top_rollouts(mppi_handle h, int system, int n, int* idx_out, fl
  */
 mppi_status mppi_replay_rollouts(mppi_handle h, int system, const int* rollout_idx, int n, float* y_out, float* step_cost_out,
                                  int* crash_out);
+
+/* ---------------------------------------------------------------- control sequences of the caller's own ------------ */
+/* What control sequences the CALLER brings would cost — the shifted previous solution, zeros, a braking manoeuvre, a library of
+ * primitives, another planner's plan — and the step every closed-loop user writes after a disturbance or a goal change: is my
+ * warm start still better than a restart?  (The reference's controllers/Primitives evaluates open-loop candidates, takes the
+ * cheapest and keeps the old plan unless the new one wins by hysteresis_cost_threshold_.)  Both calls run one launch of
+ * mppi_amd/engine/evaluate_kernel.hpp on the handle's stream behind whatever is queued there, with the model parameters, blobs and
+ * LSTM initial state the handle has now, and return after one synchronisation.  They work before the handle's first iteration and
+ * on a K-sharded handle (locally, independent of K). */
+/**
+ * cost_out[n], crash_out[n] <- the trajectory cost and the crash status after the last step of the n control sequences
+ * u[n][T][C] (host memory), each rolled out from x0[0] (x0_count == 1) or from x0[i] (x0_count == n; x0[x0_count][S], host
+ * memory).  Row i is the cost the rollout kernel gives a rollout whose controls, once clamped, are u[i]: the plugin calls in its
+ * order (initializeDynamics, initializeCosts; per step enforceConstraints once, step, computeRunningCost with the crash status
+ * threaded through; terminalCost), a serial fp32 sum over the steps, running / T + terminal / T — WITHOUT the likelihood-ratio
+ * term: a candidate is not a sample of the current distribution, there is no mean it was drawn around.  Either output may be
+ * NULL.  Every controller kind, Robust included (no feedback term is involved: this is the plain model); nothing the controller
+ * computes depends on the call.
+ * MPPI_ERR_INVALID_ARG for n < 1, n > 65536, a null x0 or u, an x0_count other than 1 or n.
+ */
+mppi_status mppi_evaluate_controls(mppi_handle h, const float* x0, int x0_count, const float* u, int n, float* cost_out,
+                                   int* crash_out);
+/**
+ * Evaluates the handle's current control sequence (what mppi_get_control_seq returns now, after any mppi_slide) and the n
+ * sequences candidates[n][T][C], all from x0[S], in one launch, and installs the cheapest candidate if it beats the current
+ * sequence by more than `hysteresis`.  Order as mppi_top_rollouts: ascending cost, ties to the lower index with the current
+ * sequence counted as the lowest, NaN after every number.  The cheapest candidate is installed only if its cost is below
+ * current - hysteresis (strictly), or if the current cost is NaN and the candidate's is not; exactly as
+ * mppi_set_nominal_control installs it (Tube: both trajectories).
+ * chosen_out: the installed candidate's index, or -1 when the current sequence stays; cost_out[n + 1]: the current sequence's
+ * cost, then the candidates'.  Either may be NULL.
+ * MPPI_ERR_INVALID_ARG for n < 1, n > 65535, a null x0 or candidates, a negative or non-finite hysteresis;
+ * MPPI_ERR_UNSUPPORTED on a Robust handle: its nominal system is chosen by the candidate-state search, and installing a sequence
+ * under it is a different feature.
+ */
+mppi_status mppi_warm_start(mppi_handle h, const float* x0, const float* candidates, int n, float hysteresis, int* chosen_out,
+                            float* cost_out);
 
 /* ---------------------------------------------------------------- linearisation ---------------------------------- */
 /* The continuous-time Jacobians of the model, A = d xdot / d x [S][S] and B = d xdot / d u [S][C], both row-major

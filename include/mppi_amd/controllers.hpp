@@ -293,6 +293,39 @@ public:
   {
     check(sampled_.calculate(h_, num_timesteps_, output_dim_, system));
   }
+  /* ---- control sequences of the caller's own (mppi_evaluate_controls / mppi_warm_start) ---- */
+  /** costs[n] (and crash[n], if asked for) of u[n][T][C] rolled out from x0[S] — one initial state for every row — or
+   *  x0[n][S]: the rollout kernel's trajectory cost without the likelihood-ratio term (a candidate is no sample of the current
+   *  distribution) */
+  std::vector<float> evaluateControls(const std::vector<float>& x0, const std::vector<float>& u, std::vector<int>* crash = nullptr)
+  {
+    const size_t row = (size_t)num_timesteps_ * control_dim_;
+    if (u.empty() || u.size() % row != 0 || x0.empty() || x0.size() % (size_t)state_dim_ != 0)
+      throw Error(MPPI_ERR_INVALID_ARG, "evaluateControls: u[n][T][C] and x0[S] or x0[n][S] expected");
+    const int n = (int)(u.size() / row);
+    std::vector<float> cost((size_t)n);
+    if (crash)
+      crash->resize((size_t)n);
+    check(mppi_evaluate_controls(h_, x0.data(), (int)(x0.size() / (size_t)state_dim_), u.data(), n, cost.data(),
+                                 crash ? crash->data() : nullptr));
+    return cost;
+  }
+  /** the current control sequence and candidates[n][T][C] evaluated from x0; the cheapest candidate is installed as
+   *  updateImportanceSampler would install it if it is more than `hysteresis` cheaper.  Returns its index, or -1 when the
+   *  current sequence stays; costs (if asked for): [n + 1], the current sequence's first */
+  int warmStart(const std::vector<float>& x0, const std::vector<float>& candidates, float hysteresis = 0.0f,
+                std::vector<float>* costs = nullptr)
+  {
+    const size_t row = (size_t)num_timesteps_ * control_dim_;
+    if (candidates.empty() || candidates.size() % row != 0 || x0.size() != (size_t)state_dim_)
+      throw Error(MPPI_ERR_INVALID_ARG, "warmStart: candidates[n][T][C] and x0[S] expected");
+    const int n = (int)(candidates.size() / row);
+    if (costs)
+      costs->resize((size_t)n + 1);
+    int chosen = -1;
+    check(mppi_warm_start(h_, x0.data(), candidates.data(), n, hysteresis, &chosen, costs ? costs->data() : nullptr));
+    return chosen;
+  }
   std::vector<float> getSampledCostSeq() const
   {
     int kl = 0;

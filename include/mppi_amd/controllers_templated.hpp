@@ -374,6 +374,44 @@ public:
     ensureHandle();
     check(sampled_.calculate(h_, params_.num_timesteps_, OUTPUT_DIM, system));
   }
+  /* ---- control sequences of the caller's own (mppi_evaluate_controls / mppi_warm_start) ---- */
+  /** costs[n] (and crash[n], if asked for) of the n sequences u rolled out from x0[0] (one initial state) or x0[i] (n of them):
+   *  the rollout kernel's trajectory cost without the likelihood-ratio term (a candidate is no sample of the current distribution) */
+  std::vector<float> evaluateControls(const std::vector<state_array>& x0, const std::vector<control_trajectory>& u,
+                                      std::vector<int>* crash = nullptr)
+  {
+    ensureHandle();
+    syncPlugins();
+    std::vector<float> xs(x0.size() * (size_t)STATE_DIM);
+    for (size_t i = 0; i < x0.size(); i++)
+      std::copy(x0[i].data(), x0[i].data() + STATE_DIM, xs.begin() + i * (size_t)STATE_DIM);
+    const std::vector<float> rows = packControlRows(u);
+    std::vector<float> cost(u.size());
+    if (crash)
+      crash->resize(u.size());
+    check(mppi_evaluate_controls(h_, xs.data(), (int)x0.size(), rows.data(), (int)u.size(), cost.data(),
+                                 crash ? crash->data() : nullptr));
+    return cost;
+  }
+  std::vector<float> evaluateControls(const state_array& x0, const std::vector<control_trajectory>& u, std::vector<int>* crash = nullptr)
+  {
+    return evaluateControls(std::vector<state_array>(1, x0), u, crash);
+  }
+  /** the current control sequence and the candidates evaluated from x0; the cheapest candidate is installed as
+   *  updateImportanceSampler would install it if it is more than `hysteresis` cheaper.  Returns its index, or -1 when the
+   *  current sequence stays; costs (if asked for): [n + 1], the current sequence's first */
+  int warmStart(const state_array& x0, const std::vector<control_trajectory>& candidates, float hysteresis = 0.0f,
+                std::vector<float>* costs = nullptr)
+  {
+    ensureHandle();
+    syncPlugins();
+    const std::vector<float> rows = packControlRows(candidates);
+    if (costs)
+      costs->resize(candidates.size() + 1);
+    int chosen = -1;
+    check(mppi_warm_start(h_, x0.data(), rows.data(), (int)candidates.size(), hysteresis, &chosen, costs ? costs->data() : nullptr));
+    return chosen;
+  }
   std::vector<float> getSampledCostSeq() const
   {
     std::vector<float> c((size_t)(kind_ == MPPI_CONTROLLER_TUBE || kind_ == MPPI_CONTROLLER_ROBUST ? 2 : 1) * NUM_ROLLOUTS);
@@ -424,6 +462,15 @@ protected:
   }
   virtual void afterCreate()
   {
+  }
+  /** [n][T][C]: the first num_timesteps_ steps of every trajectory, as mppi_set_nominal_control reads one */
+  std::vector<float> packControlRows(const std::vector<control_trajectory>& u) const
+  {
+    const size_t row = (size_t)params_.num_timesteps_ * CONTROL_DIM;
+    std::vector<float> rows(u.size() * row);
+    for (size_t i = 0; i < u.size(); i++)
+      std::copy(u[i].data(), u[i].data() + row, rows.begin() + i * row);
+    return rows;
   }
   void ensureHandle()
   {

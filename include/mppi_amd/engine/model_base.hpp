@@ -17,6 +17,7 @@
 #include "linearize_kernel.hpp"
 #include "feedback_kernel.hpp"
 #include "replay_kernel.hpp"
+#include "evaluate_kernel.hpp"
 
 namespace mppi
 {
@@ -248,6 +249,14 @@ struct ModelBase
     err = "model has no replay kernel";
     return MPPI_ERR_UNSUPPORTED;
   }
+  /** cost[a.n], crash[a.n] <- the trajectory cost (no likelihood-ratio term) and the last crash status of the a.n control sequences
+   *  a.u_d the caller brought, each from its own or from one initial state: one launch of kernels::evaluateKernel on `stream`
+   *  (engine/evaluate_kernel.hpp) in the lane form the model's trajectory re-roll uses */
+  virtual mppi_status launchEvaluate(const kernels::EvaluateArgs& a, hipStream_t stream, std::string& err)
+  {
+    err = "model has no evaluate kernel";
+    return MPPI_ERR_UNSUPPORTED;
+  }
 };
 
 /** fingerprint of the structures a model translation unit and libmppi_amd.so exchange (mppi_register_model refuses a
@@ -258,8 +267,9 @@ struct ModelBase
  *  6: FinalizeArgs::phases / carry block of the split hand-over (round 5); 7: undeclaredBarrierFreePlugins; 8: the transposed
  *  record copy (RolloutArgs) and supportsMergeControl / launchMergeControl (both round 6); 9: LaunchRecord,
  *  listReplicatedLaneShapes / supportsRMPPIPipeline (the launch and model introspection of mppi_amd.h); 10: costmapChannels;
- *  11: hasComputeGrad / launchLinearize; 12: launchDdpBackward, setFeedbackGains' gains_on_device; 13: launchReplay. */
-#define MPPI_ENGINE_ABI_VERSION 13
+ *  11: hasComputeGrad / launchLinearize; 12: launchDdpBackward, setFeedbackGains' gains_on_device; 13: launchReplay;
+ *  14: launchEvaluate. */
+#define MPPI_ENGINE_ABI_VERSION 14
 
 constexpr int engineAbiFingerprint()
 {
@@ -267,7 +277,8 @@ constexpr int engineAbiFingerprint()
          (int)(sizeof(ModelBase) + 131 * sizeof(kernels::RolloutArgs) + 131 * 131 * sizeof(kernels::FinalizeArgs) +
                7 * sizeof(kernels::RMPPIArgs) + 17 * sizeof(kernels::InitEvalArgs) + 31 * sizeof(SamplerLaunchState) +
                37 * sizeof(kernels::MergeControlArgs) + 41 * sizeof(kernels::LinearizeArgs) +
-               43 * sizeof(kernels::DdpBackwardArgs) + 47 * sizeof(kernels::ReplayArgs));
+               43 * sizeof(kernels::DdpBackwardArgs) + 47 * sizeof(kernels::ReplayArgs) +
+               53 * sizeof(kernels::EvaluateArgs));
 }
 
 }  // namespace engine

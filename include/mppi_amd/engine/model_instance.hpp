@@ -1301,6 +1301,29 @@ struct ModelT : ModelBase
                                dim3(BY == 1 ? 64 : 1, BY, 1), smem, stream, err, rd, cost, rs, a);
         });
   }
+
+  /** evaluateKernel on the same form; no sampler is involved */
+  mppi_status launchEvaluate(const kernels::EvaluateArgs& a, hipStream_t stream, std::string& err) override
+  {
+    if (!blobsReady(err))
+      return MPPI_ERR_STATE;
+    if (a.n < 1 || a.num_timesteps < 1 || !a.x0_d || !a.u_d || !a.cost_d || !a.crash_d ||
+        (a.x0_stride != 0 && a.x0_stride != DYN_T::STATE_DIM))
+      return refuse(MPPI_ERR_INVALID_ARG, "evaluateKernel: n >= 1 rows, T >= 1 steps, four device pointers, a state stride of 0 or S",
+                    err);
+    return onSingleRolloutForm(
+        [&](auto& rd, auto which) { return kernels::evaluateSharedBytes(rd, cost, decltype(which)::value == FORM_OWN ? FIN_BY : 1); },
+        [&](auto& rd, auto which, size_t smem) -> mppi_status {
+          using RD_T = std::decay_t<decltype(rd)>;
+          constexpr int BY = decltype(which)::value == FORM_OWN ? FIN_BY : 1;  // contract lanes per row
+          const char* const what[] = {"evaluateKernel (wave form)", "evaluateKernel (replicated lanes)", "evaluateKernel"};
+          if (smem > MAX_LDS_BYTES)
+            return ldsOverflow(what[which], smem, err);
+          constexpr int ROWS = BY == 1 ? kernels::evaluateBlockRows<RD_T>() : 1;
+          return launchChecked(what[which], kernels::evaluateKernel<RD_T, COST_T, BY>, dim3((a.n + ROWS - 1) / ROWS),
+                               dim3(BY == 1 ? 64 : 1, BY, 1), smem, stream, err, rd, cost, a);
+        });
+  }
 };
 
 }  // namespace engine

@@ -152,6 +152,8 @@ SIGNATURES = {
     "mppi_get_sampled_controls": (C.c_int, [H, _f32p]),
     "mppi_top_rollouts": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mppi_replay_rollouts": (C.c_int, [H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mppi_evaluate_controls": (C.c_int, [H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "mppi_warm_start": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "mppi_get_optimal_control": (C.c_int, [H, _f32p]),
     "mppi_optimize": (C.c_int, [H, C.c_int, C.c_int]),
     "mppi_upload_state": (C.c_int, [H, _f32p]),

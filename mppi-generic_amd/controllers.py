@@ -750,6 +750,46 @@ class MPPIController:
                                                    crash.ctypes.data))
         return y, cost, crash
 
+    def _control_rows(self, u, what):
+        u = np.ascontiguousarray(u, np.float32)
+        row = self.num_timesteps * self.CONTROL_DIM
+        if u.size % row != 0:
+            raise MPPIError(MPPI_ERR_INVALID_ARG, "%s: control sequences of shape (n, %d, %d) expected, got %s"
+                            % (what, self.num_timesteps, self.CONTROL_DIM, u.shape))
+        return u.reshape(-1, self.num_timesteps, self.CONTROL_DIM)
+
+    def evaluate_controls(self, x0, u):
+        """(costs (n,), crash flags (n,)) of the caller's control sequences u (n, T, C) rolled out on the device from x0 (S,) — one
+        initial state for every row — or x0 (n, S), one per row (mppi_evaluate_controls): the rollout kernel's trajectory cost of
+        a rollout whose clamped controls are u[i], without the likelihood-ratio term (a candidate is no sample of the current
+        distribution), and the crash status after the last step.  Nothing the controller computes depends on the call."""
+        u = self._control_rows(u, "evaluate_controls")
+        x = np.ascontiguousarray(x0, np.float32)
+        if x.size % self.STATE_DIM != 0:
+            raise MPPIError(MPPI_ERR_INVALID_ARG, "evaluate_controls: initial states of %d floats expected, got %s"
+                            % (self.STATE_DIM, x.shape))
+        n = u.shape[0]
+        cost = np.empty(n, np.float32)
+        crash = np.empty(n, np.int32)
+        self._check(self._lib.mppi_evaluate_controls(self._h, x.ctypes.data, x.size // self.STATE_DIM, u.ctypes.data, n,
+                                                     cost.ctypes.data, crash.ctypes.data))
+        return cost, crash
+
+    def warm_start(self, x0, candidates, hysteresis=0.0):
+        """(chosen, costs (n + 1,)): the current control sequence (getControlSeq) and the candidates (n, T, C) evaluated from x0 in
+        one launch (mppi_warm_start); the cheapest candidate is installed as setNominalControl would install it if its cost is
+        below current - hysteresis, or if the current cost is NaN and its own is not.  chosen is its index, or -1 when the
+        current sequence stays; costs[0] is the current sequence's cost.  Vanilla, Colored and Tube controllers."""
+        self._check_state_size(x0, "warm_start")
+        u = self._control_rows(candidates, "warm_start")
+        x = _f32(x0).reshape(-1)
+        n = u.shape[0]
+        chosen = C.c_int(-1)
+        cost = np.empty(n + 1, np.float32)
+        self._check(self._lib.mppi_warm_start(self._h, x.ctypes.data, u.ctypes.data, n, float(hysteresis),
+                                              C.addressof(chosen), cost.ctypes.data))
+        return chosen.value, cost
+
     def sampled_trajectories(self, top_n=0, fraction=0.0, seed=None, system=0):
         """the reference's calculateSampledStateTrajectories (controllers/controller.cu:55-179): replays slot 0 = the optimal
         sequence, then int(fraction * K) rollouts drawn without replacement from the first 98 % of the local rollouts (the last

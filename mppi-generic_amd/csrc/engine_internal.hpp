@@ -12,6 +12,8 @@
  *   engine_controllers.hip  mppi_compute_control for the Vanilla / Colored, Tube and Robust controllers, hand-over (inbox,
  *                           flags, split finalize), getters, slide
  *   engine_loop.hip         the device-resident loop (mppi_optimize), timing and kernel choice entry points
+ *   engine_replay.hip       the last iteration's sampled rollouts: top-N selection, chosen rows run again
+ *   engine_evaluate.hip     control sequences of the caller's own: their trajectory costs, the warm start chosen among them
  *   engine_exchange.hip     multi-GPU set-up: exchange buffers, P2P mailbox sessions, RCCL communicator
  *   engine_operators.hip    kernel-level operators and probes of the C ABI (normExp, weighted reduction, Philox, textures, ...)
  * Functions defined in one of them and called from another are declared at the bottom of this header, hidden from the
@@ -234,6 +236,9 @@ struct mppi_handle_s
   HipBuffer<float> top_d;          // [n] indices | [n] costs of the last selection (256 + 256 words)
   HipBuffer<float> replay_d;       // y [n][T][O] | step costs [n][T + 1] | crash flags [n][T] | the index list [n]
   std::vector<float> replay_h;     // the results on their way to the caller's arrays
+  /* mppi_evaluate_controls / mppi_warm_start (engine_evaluate.hip): empty until the first call, grown on demand */
+  HipBuffer<float> eval_d;         // control rows [n][T][C] | initial states [1 or n][S] | costs [n] | crash flags [n]
+  std::vector<float> eval_h;       // costs [n] | crash flags [n] on their way to the caller's arrays
   /* mppi_set_feedback_params / mppi_compute_feedback[_at] (engine/feedback_kernel.hpp) */
   std::vector<float> fb_params_h;  // Q [S][S] | R [C][C] | Qf [S][S]; empty: never set (identities on first use)
   bool fb_params_dirty = false;    // fb_params_h is newer than fb_params_d

@@ -17,7 +17,9 @@ in .so)
 linearize / feedback: wall clock of mppi_linearize_trajectory / mppi_compute_feedback on Cartpole T = 100 and AutoRally-NN T = 150;
 not part of the default set.
 replay: wall clock of mppi_top_rollouts(32) and mppi_replay_rollouts(33 rows) next to mppi_linearize_trajectory on Cartpole
-K = 16384, T = 100; not part of the default set.)"""
+K = 16384, T = 100; not part of the default set.
+evaluate: wall clock of mppi_evaluate_controls on n = 16384 caller-supplied control sequences, Cartpole T = 100 and AutoRally-NN
+T = 150 (both lane forms); not part of the default set.)"""
 import os
 import sys
 
@@ -237,3 +239,35 @@ if "replay" in which:
     print("cartpole   K=%d T=%d linearize_trajectory %.1f us (p10 %.1f, p90 %.1f); top_rollouts(32) %.1f us (p10 %.1f, p90 %.1f); "
           "replay_rollouts(33) %.1f us (p10 %.1f, p90 %.1f)" % ((cfg["K"], cfg["T"]) + tuple(lin) + tuple(top) + tuple(rep)), flush=True)
     eng.close()
+if "evaluate" in which:
+    # mppi_evaluate_controls on n = 16384 control sequences of the caller's own: Cartpole T = 100 (one lane per row) and AutoRally-NN
+    # T = 150 on its one-rollout-per-wave form and, with MPPI_AMD_FINALIZE_FORM=rep, on its replicated lanes.  Wall time of the whole
+    # call — the copy of the rows from pageable host memory (6.6 MB / 19.7 MB), the launch, the copy of the results back, one
+    # synchronisation — median and p10 / p90 over 200 calls after warm-up; and of a call with n = 64 rows on the same handle, which
+    # is the fixed part.  The kernel's own time is not in these figures; take it from a kernel trace of this mode, in a run of its own.
+    import time  # noqa: E402
+
+    def timed(fn, n=200):
+        t = []
+        for _ in range(n):
+            t0 = time.perf_counter()
+            fn()
+            t.append((time.perf_counter() - t0) * 1e6)
+        return tuple(np.percentile(t, [50, 10, 90]))
+
+    for name, cfg, form in (("cartpole", cartpole_cfg(K=16384, T=100), None),
+                            ("autorally", autorally_cfg(K=16384, T=150, lambda_=1.0), None),
+                            ("autorally", autorally_cfg(K=16384, T=150, lambda_=1.0), "rep")):
+        if form:
+            os.environ["MPPI_AMD_FINALIZE_FORM"] = form
+        eng = make_engine(cfg)
+        C_ = eng.CONTROL_DIM
+        u = np.random.default_rng(1).uniform(-1.0, 1.0, (16384, cfg["T"], C_)).astype(np.float32)
+        for _ in range(20):
+            eng.evaluate_controls(cfg["x0"], u)
+        big = timed(lambda: eng.evaluate_controls(cfg["x0"], u))
+        small = timed(lambda: eng.evaluate_controls(cfg["x0"], u[:64]))
+        print("%-10s n=16384 T=%d form=%s evaluate_controls %.1f us (p10 %.1f, p90 %.1f); n=64: %.1f us (p10 %.1f, p90 %.1f)"
+              % ((name, cfg["T"], form or "default") + big + small), flush=True)
+        eng.close()
+        os.environ.pop("MPPI_AMD_FINALIZE_FORM", None)
