@@ -33,10 +33,10 @@ extern "C" {
 #endif
 
 #define MPPI_AMD_VERSION_MAJOR 0
-#define MPPI_AMD_VERSION_MINOR 7 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory; 4: mppi_set_feedback_params,
+#define MPPI_AMD_VERSION_MINOR 8 /* 3: mppi_has_compute_grad, mppi_linearize, mppi_linearize_trajectory; 4: mppi_set_feedback_params,
                                     mppi_compute_feedback, mppi_compute_feedback_at; 5: mppi_create_with_sampler takes
                                     MPPI_CONTROLLER_TUBE with MPPI_SAMPLER_COLORED; 6: mppi_top_rollouts, mppi_replay_rollouts;
-                                    7: mppi_evaluate_controls, mppi_warm_start */
+                                    7: mppi_evaluate_controls, mppi_warm_start; 8: mppi_texture3d_query */
 
 typedef struct mppi_handle_s* mppi_handle;
 
@@ -750,6 +750,24 @@ typedef struct mppi_texture2d_params
  *  coordinate (queryTexture), 1 = map pose (queryTextureAtMapPose), 2 = world pose (queryTextureAtWorldPose);
  *  out[n][channels] */
 mppi_status mppi_texture2d_query(const float* data, int width, int height, int channels, const mppi_texture2d_params* p,
+                                 const float* points, int n, int frame, float* out, int device);
+
+/** mppi_texture2d_params for a volume: a third address mode (z also takes 2 = wrap, with the reference's period depth - 1) */
+typedef struct mppi_texture3d_params
+{
+  int address_mode[3];   /* x, y: 0 clamp (default), 1 border; z: 0, 1 or 2 wrap */
+  int filter_mode;       /* 0 linear (default), 1 point */
+  float border_color[4];
+  float origin[3];
+  float rotations[9];    /* row-major 3x3, world -> map */
+  float resolution[3];   /* metres per texel along x, y, z */
+} mppi_texture3d_params;
+/** ThreeDTextureHelper lookups on the device (utils/texture_helpers/three_d_texture_helper.hpp; reference:
+ *  three_d_texture_helper.cu:135-282, the fp32 host formula): data[depth][height][width][channels] (channels 1 or 4),
+ *  points[n][3], frame as mppi_texture2d_query; out[n][channels].  Frame 3 + N (N = 1, 3, 4) is the batch form at world poses,
+ *  queryTextureAtWorldPoseBatch<N>, n a multiple of N.  Wrap on x or y (the reference's host path throws), wrap on a one-layer
+ *  volume and extents below 2 return MPPI_ERR_INVALID_ARG */
+mppi_status mppi_texture3d_query(const float* data, int width, int height, int depth, int channels, const mppi_texture3d_params* p,
                                  const float* points, int n, int frame, float* out, int device);
 
 #ifdef __cplusplus

@@ -1,7 +1,7 @@
 /**
  * model_blobs.hpp — what ModelT::setBlob and ModelT::setLSTMInitialState (model_instance.hpp) are written on: the count and dims
  * checks of a blob with their refusal texts, the upload into a buffer ModelT owns, and the binding of an uploaded map and its
- * frame to a TwoDTextureHelper texture entry.  The plugin classes keep plain non-owning pointers; nothing here owns memory.
+ * frame to a TwoDTextureHelper or ThreeDTextureHelper texture entry.  The plugin classes keep plain non-owning pointers; nothing here owns memory.
  */
 #ifndef MPPI_AMD_MODEL_BLOBS_HPP_
 #define MPPI_AMD_MODEL_BLOBS_HPP_
@@ -38,9 +38,44 @@ inline bool expectFrameCount(const std::string& name, size_t count, std::string&
 }
 
 /** a row-major map of `channels` floats per texel: dims {height, width}, or {height, width, channels} (interleaved texels) when
- *  there is more than one channel, with a product equal to count */
-inline bool checkMapDims(const std::string& name, const int* dims, int ndims, size_t count, int channels, std::string& err)
+ *  there is more than one channel, with a product equal to count.
+ *  spatial_rank == 3, a volume: dims {depth, height, width}, or {depth, height, width, channels}.  Refused, each with its own
+ *  text: another rank; a channel count other than 1 or 4 (a texel is a float or a float4); a channel count other than the one
+ *  the model reads; an extent of zero or less; a product other than count or beyond a 32-bit texel index. */
+inline bool checkMapDims(const std::string& name, const int* dims, int ndims, size_t count, int channels, std::string& err,
+                         int spatial_rank = 2)
 {
+  if (spatial_rank == 3)
+  {
+    if (ndims != 3 && ndims != 4)
+    {
+      err = name + ": dims must be {depth, height, width} or {depth, height, width, channels}, got rank " + std::to_string(ndims);
+      return false;
+    }
+    const int given = ndims == 4 ? dims[3] : 1;
+    if (given != 1 && given != 4)
+    {
+      err = name + ": a volume has 1 or 4 channels per texel, got " + std::to_string(given);
+      return false;
+    }
+    if (given != channels)
+    {
+      err = name + ": this model reads " + std::to_string(channels) + " channel(s) per texel, got " + std::to_string(given);
+      return false;
+    }
+    if (dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0)
+    {
+      err = name + ": every extent of {depth, height, width} must be positive";
+      return false;
+    }
+    const unsigned long long texels = (unsigned long long)dims[0] * (unsigned long long)dims[1] * (unsigned long long)dims[2] * channels;
+    if (texels != count || texels > 0x7fffffffULL)
+    {
+      err = name + ": depth*height*width*channels must equal count and fit a 32-bit index";
+      return false;
+    }
+    return true;
+  }
   const bool ok = ndims == (channels == 1 ? 2 : 3) && dims[0] > 0 && dims[1] > 0 && (channels == 1 || dims[2] == channels) &&
                   (size_t)dims[0] * dims[1] * channels == count;
   if (ok)
@@ -91,6 +126,17 @@ inline void bindMap(TEX& tex, const HipBuffer<float>& buffer, const int* dims, m
   tex.data = buffer;
   tex.height = dims[0];
   tex.width = dims[1];
+  tex.use = (st == MPPI_OK);
+}
+
+/** bindMap for a volume entry (ThreeDTextureHelper): dims {depth, height, width, ...} */
+template <class TEX>
+inline void bindVolume(TEX& tex, const HipBuffer<float>& buffer, const int* dims, mppi_status st)
+{
+  tex.data = buffer;
+  tex.depth = dims[0];
+  tex.height = dims[1];
+  tex.width = dims[2];
   tex.use = (st == MPPI_OK);
 }
 

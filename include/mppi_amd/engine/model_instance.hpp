@@ -477,6 +477,7 @@ struct ModelT : ModelBase
   static_assert(!(has_costmap<COST_T>::value && has_cost_texture<COST_T>::value),
                 "a cost class takes its map as costmap_d_ or through a tex_helper_, not both");
   HipBuffer<float> costmap_d;
+  HipBuffer<float> cost_volume_d;
   HipBuffer<float> elevation_d;
   HipBuffer<float> normals_d;
   bool normals_transform_set = false;
@@ -680,6 +681,25 @@ struct ModelT : ModelBase
         if (!expectFrameCount(name, count, err))
           return MPPI_ERR_INVALID_ARG;
         setMapFrame(cost.tex_helper_.textures_[0], data);
+        return MPPI_OK;
+      }
+    }
+    if constexpr (has_cost_volume<COST_T>::value)
+    {
+      /* the cost's ThreeDTextureHelper: {depth, height, width} values, row-major layers; the model runs without it */
+      if (name == "cost_volume")
+      {
+        if (!checkMapDims(name, dims, ndims, count, std::remove_reference_t<decltype(cost.volume_helper_)>::CHANNELS, err, 3))
+          return MPPI_ERR_INVALID_ARG;
+        const mppi_status st = uploadBlob(cost_volume_d, data, count, stream, err);
+        bindVolume(cost.volume_helper_.textures_[0], cost_volume_d, dims, st);
+        return st;
+      }
+      if (name == "cost_volume_transform")
+      {
+        if (!expectFrameCount(name, count, err))
+          return MPPI_ERR_INVALID_ARG;
+        setMapFrame(cost.volume_helper_.textures_[0], data);
         return MPPI_OK;
       }
     }

@@ -130,6 +130,15 @@ template <class T>
 struct has_cost_texture<T, std::void_t<decltype(std::declval<T&>().tex_helper_.textures_[0].data)>> : std::true_type
 {
 };
+template <class T, class = void>
+struct has_cost_volume : std::false_type
+{
+};
+/** a cost with a ThreeDTextureHelper member `volume_helper_` (QuadrotorVolumeCost: the clearance volume) */
+template <class T>
+struct has_cost_volume<T, std::void_t<decltype(std::declval<T&>().volume_helper_.textures_[0].depth)>> : std::true_type
+{
+};
 
 }  // namespace engine
 }  // namespace mppi

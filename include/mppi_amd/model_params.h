@@ -17,6 +17,8 @@
  *                                      (CostParams<4> base; use_euler, the reference's bool, as an int)
  *   mppi_quadrotor_map_cost_params  <- QuadrotorMapCostParams        cost_functions/quadrotor/quadrotor_map_cost.cuh:14-60
  *                                      (CostParams<4> base; float3 / float4 as 3 / 4 floats each)
+ *   mppi_quadrotor_volume_cost_params  (no counterpart in the reference: QuadrotorVolumeCostParams of this project,
+ *                                      mppi_quadrotor_cost_params + three fields)
  *   mppi_ar_robust_cost_params      <- ARRobustCostParams            cost_functions/autorally/ar_robust_cost.cuh:6-29
  *                                      (ARStandardCostParams base + heading_coeff)
  * (paths relative to the reference's include/mppi/).
@@ -238,6 +240,28 @@ typedef struct mppi_quadrotor_map_cost_params
   float track_boundary_cost;   /* 2.5 */
   float gate_width;            /* 2.15 m */
 } mppi_quadrotor_map_cost_params;
+
+/** QuadrotorVolumeCost (cost_functions/quadrotor/quadrotor_volume_cost.hpp; not in the reference): QuadrotorQuadraticCost plus a
+ *  clearance volume sampled at the vehicle's position.  The volume and its frame are the "cost_volume" and
+ *  "cost_volume_transform" blobs of mppi_set_model_blob(). */
+typedef struct mppi_quadrotor_volume_cost_params
+{
+  float control_cost_coeff[4]; /* {2, 2, 2, 2} */
+  float discount;              /* 1.0 */
+  float s_goal[13];            /* as mppi_quadrotor_cost_params */
+  float x_coeff;               /* 1 */
+  float v_coeff;               /* 1 */
+  int use_euler;               /* 1 */
+  float q_coeff;               /* 1 */
+  float roll_coeff;            /* 1 */
+  float pitch_coeff;           /* 1 */
+  float yaw_coeff;             /* 1 */
+  float w_coeff;               /* 1 */
+  float terminal_cost_coeff;   /* 0 */
+  float volume_coeff;          /* 10: times max(0, v), v the volume's value at the position */
+  float crash_threshold;       /* 0.9: v above this adds crash_coeff */
+  float crash_coeff;           /* 1000 */
+} mppi_quadrotor_volume_cost_params;
 
 #ifdef __cplusplus
 }

@@ -8,12 +8,12 @@ from . import buildlib as _buildlib
 from .buildlib import build
 from .capi import (MPPI_OK, MPPI_ERR_INVALID_ARG, MPPI_ERR_UNKNOWN_MODEL, MPPI_ERR_NO_DEVICE, MPPI_ERR_HIP, MPPI_ERR_LAUNCH_SHAPE,
                    MPPI_ERR_LDS_OVERFLOW, MPPI_ERR_STATE, MPPI_ERR_NAN, MPPI_ERR_COMM, MPPI_ERR_UNSUPPORTED,
-                   MppiTexture2dParams, MppiConfig, MppiGaussianParams, MppiStats, MppiSystemStats, SIGNATURES, library_path, load_library)
+                   MppiTexture2dParams, MppiTexture3dParams, texture3d_query, MppiConfig, MppiGaussianParams, MppiStats, MppiSystemStats, SIGNATURES, library_path, load_library)
 from .controllers import (MPPI_KERNEL_AUTO, MPPI_KERNEL_FUSED, MPPI_KERNEL_PIPELINE, MPPI_CONTROLLER_TUBE, MPPI_CONTROLLER_VANILLA, MPPI_NOISE_INJECTED, MPPI_NOISE_PHILOX_FUSED,
                           MPPIError, MPPIController, TubeMPPIController, VanillaMPPIController, ColoredMPPIController, RobustMPPIController,
                           MPPI_CONTROLLER_COLORED, CartpoleDynamicsParams,
                           CartpoleQuadraticCostParams, DoubleIntegratorParams, DoubleIntegratorCircleCostParams,
-                          QuadrotorDynamicsParams, QuadrotorQuadraticCostParams, QuadrotorMapCostParams, set_cost_texture, det_atan2,
+                          QuadrotorDynamicsParams, QuadrotorQuadraticCostParams, QuadrotorMapCostParams, QuadrotorVolumeCostParams, set_cost_texture, set_cost_volume, det_atan2,
                           ARStandardCostParams, ARRobustCostParams, RacerDubinsParams, RacerDubinsElevationParams, RacerDubinsSuspensionParams, RacerDubinsUncertaintyParams, QuadraticCostParams28, fnn_blob_from_npz_dict, lstm_blob_from_npz_dict,
                           det_eval, LSTMLSTMHelper, texture2d_query, npz_read_array, philox_normal, launch_boundary_us, issue_interval_ns, norm_exp, compute_weights, weighted_reduction,
                           compute_weights_reference_order, weighted_reduction_reference_order,

@@ -185,6 +185,8 @@ SIGNATURES = {
     "mppi_measure_issue_interval": (C.c_int, [C.c_int, C.POINTER(C.c_float)]),
     "mppi_det_eval": (C.c_int, [C.c_int, _f32p, _f32p, C.c_int, C.c_int]),
     "mppi_texture2d_query": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, _f32p, C.c_int, C.c_int, _f32p, C.c_int]),
+    "mppi_texture3d_query": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _f32p, C.c_int, C.c_int, _f32p,
+                                       C.c_int]),
 }
 
 class MppiTexture2dParams(C.Structure):
@@ -193,6 +195,22 @@ class MppiTexture2dParams(C.Structure):
                 ("origin", C.c_float * 3), ("rotations", C.c_float * 9), ("resolution", C.c_float * 3)]
 
     def __init__(self, origin=(0, 0, 0), rotations=(1, 0, 0, 0, 1, 0, 0, 0, 1), resolution=(1, 1, 1), address_mode=(0, 0),
+                 filter_mode=0, border_color=(0, 0, 0, 0)):
+        super().__init__()
+        self.origin[:] = origin
+        self.rotations[:] = rotations
+        self.resolution[:] = resolution
+        self.address_mode[:] = address_mode
+        self.filter_mode = filter_mode
+        self.border_color[:] = border_color
+
+
+class MppiTexture3dParams(C.Structure):
+    """mppi_texture3d_params: MppiTexture2dParams with a third address mode (z also takes 2 = wrap)"""
+    _fields_ = [("address_mode", C.c_int * 3), ("filter_mode", C.c_int), ("border_color", C.c_float * 4),
+                ("origin", C.c_float * 3), ("rotations", C.c_float * 9), ("resolution", C.c_float * 3)]
+
+    def __init__(self, origin=(0, 0, 0), rotations=(1, 0, 0, 0, 1, 0, 0, 0, 1), resolution=(1, 1, 1), address_mode=(0, 0, 0),
                  filter_mode=0, border_color=(0, 0, 0, 0)):
         super().__init__()
         self.origin[:] = origin
@@ -229,3 +247,23 @@ def load_library(build_if_missing=True):
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def texture3d_query(data, points, frame, params=None, device=0, batch=0):
+    """ThreeDTextureHelper lookups on the device (mppi_texture3d_query): data[d][h][w] or [d][h][w][channels], points[n][3],
+    frame 0 texture coordinate / 1 map pose / 2 world pose; batch = 1, 3 or 4: queryTextureAtWorldPoseBatch<batch> at world
+    poses, n a multiple of it.  Returns out[n][channels]; raises MPPIError when the library refuses."""
+    from .controllers import MPPIError
+    lib = load_library()
+    d = np.ascontiguousarray(data, np.float32)
+    if d.ndim == 3:
+        d = d[:, :, :, None]
+    depth, h, w, ch = d.shape
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    out = np.zeros((pts.shape[0], ch), np.float32)
+    p = params if params is not None else MppiTexture3dParams()
+    st = lib.mppi_texture3d_query(d.reshape(-1), w, h, depth, ch, C.byref(p), pts.reshape(-1), pts.shape[0],
+                                  3 + batch if batch else frame, out.reshape(-1), device)
+    if st != MPPI_OK:
+        raise MPPIError(st, (lib.mppi_last_error(None) or b"").decode())
+    return out

@@ -202,6 +202,36 @@ def set_cost_texture(controller, costmap, origin=(0.0, 0.0, 0.0), rotations=None
     controller.setModelBlob("costmap", cm)
 
 
+class QuadrotorVolumeCostParams(C.Structure):
+    """mppi_quadrotor_volume_cost_params (QuadrotorVolumeCost, not in the reference): QuadrotorQuadraticCostParams and the three
+    fields of the clearance-volume term, volume_coeff * max(0, v) and crash_coeff where v > crash_threshold; the volume and its
+    frame are the "cost_volume" / "cost_volume_transform" blobs (set_cost_volume)."""
+    _fields_ = QuadrotorQuadraticCostParams._fields_ + [("volume_coeff", C.c_float), ("crash_threshold", C.c_float),
+                                                        ("crash_coeff", C.c_float)]
+
+    def __init__(self):
+        super().__init__()
+        self.control_cost_coeff[:] = [2.0] * 4
+        self.discount = 1.0
+        self.s_goal[:] = [0.0] * 6 + [1.0] + [0.0] * 6
+        self.x_coeff = self.v_coeff = self.q_coeff = self.w_coeff = 1.0
+        self.roll_coeff = self.pitch_coeff = self.yaw_coeff = 1.0
+        self.use_euler = 1
+        self.terminal_cost_coeff = 0.0
+        self.volume_coeff, self.crash_threshold, self.crash_coeff = 10.0, 0.9, 1000.0
+
+
+def set_cost_volume(controller, volume, origin=(0.0, 0.0, 0.0), rotations=None, resolution=(1.0, 1.0, 1.0)):
+    """the volume of a cost that samples it through a ThreeDTextureHelper (QuadrotorVolumeCost): volume [depth][height][width],
+    and its frame as in set_cost_texture, as the "cost_volume" and "cost_volume_transform" blobs of mppi_set_model_blob"""
+    v = _f32(volume)
+    assert v.ndim == 3, v.shape
+    rot = np.eye(3, dtype=np.float32) if rotations is None else _f32(rotations).reshape(3, 3)
+    frame = np.concatenate([_f32(origin).reshape(3), rot.reshape(9), _f32(resolution).reshape(3)])
+    controller.setModelBlob("cost_volume_transform", frame)
+    controller.setModelBlob("cost_volume", v)
+
+
 class RacerDubinsParams(C.Structure):
     """mppi_racer_dubins_params (reference: dynamics/racer_dubins/racer_dubins.cuh:67-87)"""
     _fields_ = [("c_t", C.c_float * 3), ("c_b", C.c_float * 3), ("c_v", C.c_float * 3), ("c_0", C.c_float),

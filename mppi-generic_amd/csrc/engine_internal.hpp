@@ -45,6 +45,7 @@
 #include "exact_reduce_kernels.hpp"
 static_assert(mppi::kernels::STATS_STRIDE == mppi::kernels::MERGE_CONTROL_STATS, "mergeControlKernel writes the statistics block");
 #include "mppi_amd/utils/texture_helpers/two_d_texture_helper.hpp"
+#include "mppi_amd/utils/texture_helpers/three_d_texture_helper.hpp"
 #include "mppi_amd/utils/nn_helpers/lstm_lstm_helper.hpp"
 
 using namespace mppi;

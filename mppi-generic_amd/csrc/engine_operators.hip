@@ -350,6 +350,87 @@ mppi_status mppi_texture2d_query(const float* data, int width, int height, int c
 }
 
 extern "C++" {
+/** frame 0 / 1 / 2 as texture2dQueryKernel; BATCH > 0: thread i takes points [i * BATCH, (i + 1) * BATCH) through the batch form */
+template <int NC, int BATCH>
+__global__ void texture3dQueryKernel(mppi::texture::ThreeDTextureHelper<1, NC> helper, const float* __restrict__ points, int n,
+                                     int frame, float* __restrict__ out)
+{
+  constexpr int PER = BATCH > 0 ? BATCH : 1;
+  const int groups = n / PER;
+  for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x)
+  {
+    float pt[PER][3], r[PER * NC];
+    for (int b = 0; b < PER; b++)
+      for (int k = 0; k < 3; k++)
+        pt[b][k] = points[((size_t)g * PER + b) * 3 + k];
+    if (BATCH > 0)
+      helper.template queryTextureAtWorldPoseBatch<PER>(0, pt, r);
+    else if (frame == 0)
+      helper.queryTexture(0, pt[0], r);
+    else if (frame == 1)
+      helper.queryTextureAtMapPose(0, pt[0], r);
+    else
+      helper.queryTextureAtWorldPose(0, pt[0], r);
+    for (int k = 0; k < PER * NC; k++)
+      out[(size_t)g * PER * NC + k] = r[k];
+  }
+}
+
+template <int NC>
+static mppi_status texture3dQuery(const float* data, int width, int height, int depth, const mppi_texture3d_params* p,
+                                  const float* points, int n, int frame, float* out)
+{
+  HipBuffer<float> dd, dp, dout;
+  const size_t texels = (size_t)width * height * depth * NC;
+  OP_TRY(dd.alloc(texels));
+  OP_TRY(dp.alloc((size_t)3 * n));
+  OP_TRY(dout.alloc((size_t)n * NC));
+  OP_TRY(hipMemcpy(dd, data, sizeof(float) * texels, hipMemcpyHostToDevice));
+  OP_TRY(hipMemcpy(dp, points, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+  mppi::texture::ThreeDTextureHelper<1, NC> helper;
+  mppi::texture::TextureParams3D& t = helper.textures_[0];
+  t.data = dd;
+  t.width = width;
+  t.height = height;
+  t.depth = depth;
+  t.use = 1;
+  memcpy(t.address_mode, p->address_mode, sizeof(t.address_mode));
+  t.filter_mode = p->filter_mode;
+  memcpy(t.border_color, p->border_color, sizeof(t.border_color));
+  memcpy(t.origin, p->origin, sizeof(t.origin));
+  memcpy(t.rotations, p->rotations, sizeof(t.rotations));
+  memcpy(t.resolution, p->resolution, sizeof(t.resolution));
+  const int batch = frame >= 3 ? frame - 3 : 0;
+  const dim3 grid((n / (batch ? batch : 1) + 255) / 256), block(256);
+  if (batch == 0)
+    hipLaunchKernelGGL((texture3dQueryKernel<NC, 0>), grid, block, 0, 0, helper, dp, n, frame, dout);
+  else if (batch == 1)
+    hipLaunchKernelGGL((texture3dQueryKernel<NC, 1>), grid, block, 0, 0, helper, dp, n, frame, dout);
+  else if (batch == 3)
+    hipLaunchKernelGGL((texture3dQueryKernel<NC, 3>), grid, block, 0, 0, helper, dp, n, frame, dout);
+  else
+    hipLaunchKernelGGL((texture3dQueryKernel<NC, 4>), grid, block, 0, 0, helper, dp, n, frame, dout);
+  OP_TRY(hipGetLastError());
+  OP_TRY(hipMemcpy(out, dout, sizeof(float) * n * NC, hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+}  // extern "C++"
+
+mppi_status mppi_texture3d_query(const float* data, int width, int height, int depth, int channels, const mppi_texture3d_params* p,
+                                 const float* points, int n, int frame, float* out, int device)
+{
+  const int batch = frame >= 3 ? frame - 3 : 0;
+  if (!data || !p || !points || !out || n <= 0 || width < 2 || height < 2 || depth < 2 || frame < 0 ||
+      (frame >= 3 && batch != 1 && batch != 3 && batch != 4) || (batch && n % batch != 0) || (channels != 1 && channels != 4) ||
+      (p->filter_mode != 0 && p->filter_mode != 1) || !mppi::texture::extentIndexable(width, height, depth, channels) ||
+      !mppi::texture::addressModesRefusal(p->address_mode, depth).empty())
+    return MPPI_ERR_INVALID_ARG;
+  MPPI_TRY(opDevice(device));
+  return channels == 1 ? texture3dQuery<1>(data, width, height, depth, p, points, n, frame, out) :
+                         texture3dQuery<4>(data, width, height, depth, p, points, n, frame, out);
+}
+
+extern "C++" {
 __global__ void boundaryProbeKernel(int* sink)
 {
   if (sink && threadIdx.x == 1024)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times optimisation iterations of the registered workloads for several block shapes (HIP events on the engine's
-stream).  Usage: python tools/time_workloads.py [cartpole|autorally|autorally-robust|di|lstm|racer|quadrotor|quadrotor-map|nln|nln-gaussian] ...
+stream).  Usage: python tools/time_workloads.py [cartpole|autorally|autorally-robust|di|lstm|racer|quadrotor|quadrotor-map|quadrotor-volume|nln|nln-gaussian] ...
 (nln / nln-gaussian: the Cartpole pipeline kernel at K = 16384, T = 100 with the NLN and with the Gaussian sampler, one workload
 each so that a kernel trace of either holds one rollout kernel; not part of the default set.
 quadrotor: the reference's hover configuration at 2048 x 150 and 16384 x 150, each beside the double integrator at the same K and T
@@ -9,6 +9,9 @@ examples/quadrotor_model/quadrotor_model.hip, built and loaded here.
 quadrotor-map: QuadrotorMapCost on the three-gate course and track map of examples/templated_quadrotor_map.hip at the same two
 sizes, registration unit examples/quadrotor_model/quadrotor_map_model.hip; an argument ending in .so is another build of that
 unit to load in its place, for an A/B of two builds of the cost.
+quadrotor-volume: QuadrotorVolumeCost (QuadrotorQuadraticCost + a 64 x 64 x 16 clearance volume through ThreeDTextureHelper) at
+K = 16384, T = 100, beside "quadrotor_map" (its course and track map) and "quadrotor" (the hover cost) at the same K, T and dt in
+the same run; registration unit examples/quadrotor_model/quadrotor_volume_model.hip.
 autorally-robust: "autorally_nn_robust" (ARRobustCost on a four-channel 600 x 600 map over the standard track map's extent) at
 K = 16384, T = 150 — the vanilla iteration on the default MFMA shape, fused and role-pipelined, and Robust MPPI's computeControl
 (wall clock around the call, which returns after the control is on the host) — each beside "autorally_nn" with ARStandardCost in
@@ -118,6 +121,36 @@ if "quadrotor-map" in which:
                    cost=course_params(), ranges=None, std_dev=[0.5, 0.5, 0.5, 2.0], control_cost_coeff=[1.0] * 4, x0=x0,
                    blobs={"costmap_transform": frame, "costmap": values})
         run("quadrotor-map", cfg, [(64, 1, 1), (64, 1, 2), (32, 4, 1)], n=50)
+if "quadrotor-volume" in which:
+    import mppi_generic_amd as m  # noqa: E402
+    import quadrotor_map_oracle  # noqa: E402
+    import quadrotor_oracle  # noqa: E402
+    import texture3d_oracle  # noqa: E402
+    from test_quadrotor import hover_cfg  # noqa: E402
+    from test_templated_quadrotor_map import course_map, course_params  # noqa: E402
+    for loader in (texture3d_oracle, quadrotor_map_oracle, quadrotor_oracle):
+        loader.load_model(m)
+    K, T = 16384, 100
+    x0 = np.zeros(13, np.float32)
+    x0[2], x0[6] = 1.0, 1.0
+    # a pillar at (3, 0) in 0.125 m cells over x in [-1, 7), y in [-4, 4), z in [0, 2): the rollouts from (0, 0, 1) cross cells and layers
+    X, Y = np.meshgrid(-1 + 0.125 * (np.arange(64) + 0.5), -4 + 0.125 * (np.arange(64) + 0.5))
+    layer = np.maximum(0.0, 1.0 - np.hypot(X - 3.0, Y) / 2.0).astype(np.float32)
+    volume = np.ascontiguousarray(np.broadcast_to(layer[None], (16, 64, 64)) * np.linspace(1.0, 0.5, 16, dtype=np.float32)[:, None, None])
+    vol_cost = m.QuadrotorVolumeCostParams()
+    hover = hover_cfg()
+    for f, _ in m.QuadrotorQuadraticCostParams._fields_:
+        setattr(vol_cost, f, getattr(hover["cost"], f))
+    base = dict(K=K, T=T, D=1, dt=0.02, lambda_=5.0, alpha=0.0, num_iters=1, dyn=m.QuadrotorDynamicsParams(), ranges=None,
+                std_dev=[0.5, 0.5, 0.5, 2.0], control_cost_coeff=[1.0] * 4, x0=x0)
+    values, frame = course_map()
+    for name, cfg in (("quadrotor-volume", dict(base, model="quadrotor_volume", cost=vol_cost,
+                                                blobs={"cost_volume_transform": texture3d_oracle.frame15([-1, -4, 0], np.eye(3), [0.125] * 3),
+                                                       "cost_volume": volume})),
+                      ("quadrotor-map", dict(base, model="quadrotor_map", cost=course_params(),
+                                             blobs={"costmap_transform": frame, "costmap": values})),
+                      ("quadrotor", dict(base, model="quadrotor", cost=hover["cost"]))):
+        run(name, cfg, [(64, 1, 1), (64, 1, 2)], n=50)
 if "autorally-robust" in which:
     import time  # noqa: E402
     import mppi_generic_amd as m  # noqa: E402
